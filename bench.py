@@ -6,7 +6,10 @@ stats -> reward -> done/auto-reset -> cropped one-hot observation written to HBM
 BASELINE configs[1]: binary-narrow 16x16, 4096 envs on one GPU, uniform random actions, auto-reset.
 Inputs (actions) are resident in HBM before the timed region; outputs (obs/reward/done/stats) are written to HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR: the outputs of the last timed step as DIR/<name>.npy (float32 / float64).  Inputs are seeded (env seeds,
+action pools, injected maps), so two builds run with the same arguments can be compared output for output.
 
 N > 1: one process per GPU.  Started by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 the script is one rank (RANK / LOCAL_RANK / WORLD_SIZE from the environment); started plainly it launches the N
@@ -127,6 +130,43 @@ def solver_active_actions(cells, pool, seed):
 
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files of one run together (data + .npy headers)
+DUMP_SAMPLE_SEED = 20240521    # --dump-outputs: which envs go into the files when not all of them fit
+
+
+def dump_outputs(out_dir, per_env, shared, rank, world):
+    """--dump-outputs: write what the timed path handed its caller in its last step as <out_dir>/<name>.npy.
+
+    `per_env`: name -> (device tensor with the env index as its first axis, numpy dtype float32 / float64); `shared`: name ->
+    host array that is not per env (written by rank 0 only).  When the per-env arrays of all envs exceed this rank's share of
+    DUMP_LIMIT_BYTES, a fixed, seeded sample of envs (the same envs in every array, in ascending order) is written instead;
+    `env_sample` then holds their indices.  With N > 1 ranks every rank writes its own shard as <name>.rank<r>.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    header = 128  # bytes of one .npy header (numpy pads the header to a multiple of 64; short shapes fit 128)
+    budget = DUMP_LIMIT_BYTES // world - header * (len(per_env) + 1)
+    if rank == 0:
+        budget -= sum(header + np.asarray(a).size * 8 for a in shared.values())
+    n = next(iter(per_env.values()))[0].shape[0]
+    row_bytes = sum(t[0].numel() * np.dtype(dt).itemsize for t, dt in per_env.values())
+    idx = None
+    if n * row_bytes > budget:
+        m = max(1, budget // (row_bytes + 8))  # (+ the float64 index of each sampled env)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        np.save(os.path.join(out_dir, f"env_sample{suffix}.npy"), idx.astype(np.float64))
+    written = []
+    for name, (t, dt) in per_env.items():
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.cpu().numpy().astype(dt))
+        written.append(name)
+    if rank == 0:
+        for name, a in shared.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+            written.append(name)
+    return {"dir": out_dir, "arrays": written, "envs": n if idx is None else int(len(idx)), "of_envs": n}
 
 
 def main():
@@ -178,7 +218,14 @@ def main():
                     help="sokoban-wide-solver: also time this many steps of the same workload through pcgrl_rollout (8 steps per launch "
                          "between re-injections) and through sub_batches = 4 (secondary object `solver_active_forms`); 0 = skip")
     ap.add_argument("--no-pin", action="store_true", help="do not pin each rank to its own slice of the host cores")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path handed its caller in its last step (obs, reward, done, "
+                         "stats; status with --solver-budget; stats only for the stats-for-grids workloads; obs, and stats when a "
+                         "refresh ran, for -evo) plus the timed region's episode sums as DIR/<name>.npy in float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 10**6} MB in all (a fixed, seeded sample of envs when all of them do not fit)")
     args = ap.parse_args()
+    if args.steps == 0:
+        ap.error("--steps must be at least 1 (or negative for the default)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
@@ -307,6 +354,9 @@ def main():
         env.reset(init_grids=inject)
     else:
         env.reset()
+    if args.dump_outputs:  # (rows the timed path may leave unwritten -- busy envs, update-only steps -- are dumped as zeros)
+        for t in (env._reward, env._done, env._stats):
+            t.zero_()
     # bfs-active: the turtle eventually overwrites the player / key / door, so the maps are re-injected; solver-active:
     # the edits wear the rooms down (a wall on a crate ends playability), so they come back every few steps
     REINJECT = 8 if solver_active else 128
@@ -743,6 +793,20 @@ def main():
     _, per_rank_eps = max_over_ranks(float(local_eps[0]))
     _, per_rank_kernel_ms = max_over_ranks(kernel_ms)
     _, per_rank_exchange_ms = max_over_ranks(exchange_ms)
+    dumped = None
+    if args.dump_outputs:  # before anything else steps this env (the first-replay and closed-loop figures below do)
+        f32, f64 = np.float32, np.float64
+        if sfg:
+            per_env = {"stats": (sfg_out, f64)}
+        elif evo:
+            per_env = {"obs": (env._obs, f32)}
+            if K >= EVO_K:  # (the timed steps restart at update 0: a refresh ran in them only if there were EVO_K of them)
+                per_env["stats"] = (env._stats, f64)
+        else:
+            per_env = {"obs": (env._obs, f32), "reward": (env._reward, f32), "done": (env._done, f32), "stats": (env._stats, f64)}
+            if budget > 0:
+                per_env["status"] = (status_rows[K - 1], f32)
+        dumped = dump_outputs(args.dump_outputs, per_env, {"episode_sums": ep_host.tolist()}, rank, world)
     first_replay_ms = measure_first_replay()
     _, per_rank_first = max_over_ranks(first_replay_ms if first_replay_ms is not None else float("nan"))
     closed = measure_closed_loop()
@@ -871,6 +935,8 @@ def main():
                 out["solver_active_forms"] = {"error": repr(exc)}
         if rollout is not None:
             out["open_loop_rollout"] = rollout
+        if dumped is not None:
+            out["dump_outputs"] = dumped
     if use_coll:
         dist.barrier()
         dist.destroy_process_group()

@@ -486,3 +486,32 @@ def test_rollout_by_shape_at_batches_beyond_one_round(problem, rep, n):
             assert np.array_equal(obs.cpu().numpy(), oobs)
     assert np.array_equal(env.get_state().grids.cpu().numpy().reshape(n, -1), orc.get_state()["grids"])
     env.check_errors()
+
+
+# ------------------------------------------------------------------------------------- bench.py --dump-outputs
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """`bench.py --steps 20 --warmup 5 --dump-outputs DIR` (the driver's step counts): the files hold the observation, reward,
+    done and stats of the last timed step -- the oracle, driven with the bench's own seeds and action rows (warm-up rows
+    0..4, then timed rows 0..19), ends on the same values -- and a second run writes the same arrays."""
+    from control_pcgrl_amd.dist import shard_seeds
+    n, args = 512, ["--envs", "512", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--rollout-steps", "0",
+                    "--rllib-adapter", "0", "--closed-loop-steps", "0", "--sub-batches", ""]
+    runs = []
+    for d in ("a", "b"):
+        out = _bench(*args, "--dump-outputs", str(tmp_path / d))
+        assert out["steps"] == 20 and out["warmup"] == 5 and out["ms_per_step"] > 0
+        assert out["dump_outputs"]["envs"] == n and out["dump_outputs"]["of_envs"] == n
+        runs.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = runs
+    assert set(a) == {"obs", "reward", "done", "stats", "episode_sums"} == set(b)
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    g = torch.Generator(device="cuda:0").manual_seed(1234)  # bench.py's action pool of rank 0
+    pool = torch.randint(0, 2, (1024, n), generator=g, device="cuda:0", dtype=torch.int32).cpu().numpy()
+    orc = po.OracleVecEnv("binary", "narrow", (16, 16), n, seeds=shard_seeds(0x5EED, n, 0, 1), threads=8)
+    orc.reset()
+    for row in list(range(5)) + list(range(20)):
+        oobs, orew, odone, ostats = orc.step(pool[row], auto_reset=True)
+    assert np.array_equal(a["obs"], oobs.astype(np.float32))
+    assert np.abs(a["reward"].astype(np.float64) - orew).max() <= REW_TOL
+    assert np.array_equal(a["done"], odone.astype(np.float32))
+    assert np.array_equal(a["stats"], ostats.astype(np.float64))

@@ -379,3 +379,43 @@ def test_kernel_hash_ignores_the_host_side_and_splits_the_families(tmp_path, mon
     with open(root / "control_pcgrl_amd" / "csrc" / "pcgrl_kernels2d.h", "a") as f:
         f.write("\n// 2-D kernel edit\n")
     assert bench.kernel_sources_sha16("2d") != h2
+
+
+def test_bench_dump_outputs_stays_within_its_limit_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: every file float32 / float64, all of them together within DUMP_LIMIT_BYTES; an output too large
+    for it is written as the same seeded sample of envs in every array, identical from run to run."""
+    import torch
+    import bench
+
+    def outputs(n, obs_shape):
+        g = torch.Generator().manual_seed(3)
+        return {"obs": (torch.randint(0, 2, (n,) + obs_shape, generator=g, dtype=torch.uint8), np.float32),
+                "reward": (torch.randn(n, generator=g), np.float32), "done": (torch.randint(0, 2, (n,), generator=g, dtype=torch.uint8), np.float32),
+                "stats": (torch.randint(0, 999, (n, 7), generator=g, dtype=torch.int32), np.float64)}
+
+    def files(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    small = outputs(4096, (32, 32, 3))  # the headline workload: every env fits
+    r = bench.dump_outputs(str(tmp_path / "small"), small, {"episode_sums": [1.0, 2.0, 3.0, 4.0, 5.0]}, 0, 1)
+    got = files(tmp_path / "small")
+    assert r["envs"] == r["of_envs"] == 4096 and set(got) == {"obs", "reward", "done", "stats", "episode_sums"}
+    for name, (t, dt) in small.items():
+        assert got[name].dtype == dt and np.array_equal(got[name], t.numpy().astype(dt)), name
+    big = outputs(8192, (32, 32, 9))
+    sizes = []
+    for run in ("a", "b"):
+        r = bench.dump_outputs(str(tmp_path / run), big, {"episode_sums": [0.0] * 10}, 0, 1)
+        sizes.append(sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)))
+    a, b = files(tmp_path / "a"), files(tmp_path / "b")
+    assert max(sizes) <= bench.DUMP_LIMIT_BYTES and 0 < r["envs"] < 8192
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["env_sample"].astype(np.int64)
+    assert len(idx) == r["envs"] and (np.diff(idx) > 0).all()
+    assert np.array_equal(a["obs"], big["obs"][0].numpy()[idx].astype(np.float32))
+    assert np.array_equal(a["stats"], big["stats"][0].numpy()[idx].astype(np.float64))
+    # N > 1 ranks: a shard per rank, each within its share
+    bench.dump_outputs(str(tmp_path / "r1"), big, {"episode_sums": [0.0]}, 1, 2)
+    assert sum(os.path.getsize(tmp_path / "r1" / f) for f in os.listdir(tmp_path / "r1")) <= bench.DUMP_LIMIT_BYTES // 2
+    assert "obs.rank1" in files(tmp_path / "r1") and "episode_sums" not in files(tmp_path / "r1")
