@@ -10,10 +10,12 @@ LIB_PATH = os.path.join(CSRC, "libpcgrl_amd.so")
 # translation units (compiled in parallel, see csrc/pcgrl_dispatch.h) and the headers they depend on
 UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pcgrl_k_zelda32.hip", "pcgrl_k_zelda64.hip",
          "pcgrl_k_sokoban32_8.hip", "pcgrl_k_sokoban32_16.hip", "pcgrl_k_sokoban32_32.hip",
-         "pcgrl_k_sokoban32_64.hip", "pcgrl_k_sokoban64_32.hip", "pcgrl_k_sokoban64_64.hip", "pcgrl_k_3d.hip"]
-HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h"]
+         "pcgrl_k_sokoban32_64.hip", "pcgrl_k_sokoban64_32.hip", "pcgrl_k_sokoban64_64.hip", "pcgrl_k_3d.hip",
+         "codes/pcgrl_codes.hip"]
+HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
+CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -94,13 +96,22 @@ SYMBOLS = {
     "pcgrl_version": (C.c_char_p, []),
 }
 
+# include/pcgrl_amd_codes.h: the tile-code observation form
+CODES_SYMBOLS = {
+    "pcgrl_codes_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32 * 4), C.POINTER(C.c_int32)]),
+    "pcgrl_codes_bytes": (C.c_int64, [C.c_void_p]),
+    "pcgrl_observe_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_onehot_to_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pcgrl_step_ready_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
     parallel, then linked into the shared library.  Rebuilds when a source is newer than the library.
     `out` / `defines`: development builds (tools/phase_timing.py, tools/wave_trace.py)."""
     out = out or LIB_PATH
-    srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER]
+    srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -109,10 +120,10 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     objdir = os.path.join(CSRC, "_obj" + ("_" + tag if tag else ""))
     os.makedirs(objdir, exist_ok=True)
     hdr_time = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
-    hdr_time = max(hdr_time, os.path.getmtime(HEADER))
+    hdr_time = max(hdr_time, os.path.getmtime(HEADER), os.path.getmtime(CODES_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
-        obj = os.path.join(objdir, u.replace(".hip", ".o"))
+        obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
         objs.append(obj)
         if (force or not os.path.exists(obj)
                 or os.path.getmtime(obj) < max(hdr_time, os.path.getmtime(os.path.join(CSRC, u)))):
@@ -153,7 +164,7 @@ def lib():
         if override and os.path.dirname(os.path.realpath(override)) != os.path.realpath(CSRC):
             raise RuntimeError(f"PCGRL_LIB={override}: only libraries inside {CSRC} are loaded")
         L = C.CDLL(override or LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(CODES_SYMBOLS.items()):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -20,6 +20,8 @@
 #include "pcgrl_kernels2d.h"  // U128 / Pcg (host side of the RNG), the small engine-level kernels
 #include "pcgrl_sokoban.h"    // sokoban_alloc
 #include "pcgrl_kernels3d.h"  // M3_* limits
+#include "codes/pcgrl_codes.h"
+#include "../../include/pcgrl_amd_codes.h"
 
 using namespace pcgrl;
 
@@ -1562,6 +1564,97 @@ int pcgrl_poll_error(pcgrl_handle h) {
     return fail(PCGRL_EINVAL, "device error flag set");
   }
   return PCGRL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- tile-code observations
+// include/pcgrl_amd_codes.h; the kernels live in codes/pcgrl_codes.hip
+static void codes_layout(const pcgrl_engine *h, int32_t shape[4], int *ndim, int *C, int *CS) {
+  const pcgrl_config &c = h->p.cfg;
+  const int nt = h->p.n_tiles;
+  shape[0] = shape[1] = shape[2] = shape[3] = 0;
+  if (c.problem == PCGRL_PROB_MC3DMAZE) {
+    shape[0] = c.obs_window[0];
+    shape[1] = c.obs_window[1];
+    shape[2] = c.obs_window[2];
+    shape[3] = 1;
+    *ndim = 4;
+    *C = *CS = 4;
+  } else if (c.representation == PCGRL_REP_WIDE) {
+    shape[0] = c.dims[0];
+    shape[1] = c.dims[1];
+    shape[2] = 1;
+    *ndim = 3;
+    *C = *CS = nt;
+  } else {
+    shape[0] = c.obs_window[0];
+    shape[1] = c.obs_window[1];
+    shape[2] = 1 + (c.static_tiles ? 1 : 0);
+    *ndim = 3;
+    *CS = nt + 1;
+    *C = nt + 1 + (c.static_tiles ? 1 : 0);
+  }
+}
+
+static int64_t codes_bytes_of(const pcgrl_engine *h) {
+  int32_t shape[4];
+  int nd = 0, C = 0, CS = 0;
+  codes_layout(h, shape, &nd, &C, &CS);
+  int64_t n = 1;
+  for (int i = 0; i < nd; i++) n *= shape[i];
+  return n;
+}
+
+int pcgrl_codes_shape(pcgrl_handle h, int32_t shape_out[4], int32_t *ndim_out) {
+  if (!h || !shape_out || !ndim_out) return fail(PCGRL_EINVAL, "pcgrl_codes_shape: bad arguments");
+  int nd = 0, C = 0, CS = 0;
+  codes_layout(h, shape_out, &nd, &C, &CS);
+  *ndim_out = nd;
+  return PCGRL_OK;
+}
+
+int64_t pcgrl_codes_bytes(pcgrl_handle h) { return h ? codes_bytes_of(h) : -1; }
+
+int pcgrl_observe_codes(pcgrl_handle h, uint8_t *d_codes, void *stream) {
+  if (!h || !d_codes) return fail(PCGRL_EINVAL, "pcgrl_observe_codes: bad arguments");
+  if (h->p.cfg.problem == PCGRL_PROB_MC3DMAZE)
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_observe_codes: the 3-D observation shows the overlay of the last statistics update: "
+                                    "pcgrl_observe into a one-hot buffer, then pcgrl_onehot_to_codes");
+  ON_DEVICE(h->device);
+  int32_t shape[4];
+  int nd = 0, C = 0, CS = 0;
+  codes_layout(h, shape, &nd, &C, &CS);
+  CodesArgs a;
+  a.out = d_codes;
+  a.T = (int32_t)codes_bytes_of(h);
+  a.P = 1 + C - CS;
+  a.wide = h->p.cfg.representation == PCGRL_REP_WIDE ? 1 : 0;
+  a.nt = obs_nt_for(h, (int64_t)h->p.n_envs * a.T) ? 1 : 0;  // (the one-hot kernels' rule, Params::obs16 bit 1)
+  HIPCHK(launch_codes_observe(h->p, h->lpe, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+static int onehot_to_codes(pcgrl_handle h, const uint8_t *d_onehot, int64_t n_rows, uint8_t *d_codes, void *stream) {
+  int32_t shape[4];
+  int nd = 0, C = 0, CS = 0;
+  codes_layout(h, shape, &nd, &C, &CS);
+  const int cells = (int)(h->obs_bytes / C);
+  HIPCHK(launch_onehot_to_codes(d_onehot, n_rows, cells, C, CS, d_codes, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_onehot_to_codes(pcgrl_handle h, const uint8_t *d_onehot, int64_t n_rows, uint8_t *d_codes, void *stream) {
+  if (!h || !d_onehot || !d_codes || n_rows < 0) return fail(PCGRL_EINVAL, "pcgrl_onehot_to_codes: bad arguments");
+  ON_DEVICE(h->device);
+  return onehot_to_codes(h, d_onehot, n_rows, d_codes, stream);
+}
+
+int pcgrl_step_ready_codes(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, uint8_t *d_scratch, uint8_t *d_codes,
+                           float *d_reward, uint8_t *d_done, int32_t *d_stats, uint8_t *d_status, void *stream) {
+  if (!h || !d_actions || !d_scratch || !d_codes || !d_status) return fail(PCGRL_EINVAL, "pcgrl_step_ready_codes: bad arguments");
+  const int rc = pcgrl_step_ready(h, d_actions, auto_reset, d_scratch, d_reward, d_done, d_stats, d_status, stream);
+  if (rc != PCGRL_OK) return rc;
+  ON_DEVICE(h->device);
+  return onehot_to_codes(h, d_scratch, h->p.n_envs, d_codes, stream);
 }
 
 }  // extern "C"

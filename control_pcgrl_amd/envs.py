@@ -10,7 +10,7 @@ of a shared batch).  Intended for plumbing / drop-in checks; throughput comes fr
 import numpy as np
 import torch
 
-from .vec_env import VecPcgrlEnv, _cfg_get, make_vec_env
+from .vec_env import VecPcgrlEnv, _cfg_get, codes_high, make_vec_env
 
 try:  # use the real spaces when gymnasium is installed, else shape/bounds holders with the same attributes
     from gymnasium import spaces as _spaces
@@ -65,7 +65,10 @@ class PcgrlGymEnv:
         shape = v.obs_shape[:-1] + (v.obs_shape[-1] + self._n_ctrl_planes,)
         # ToImage takes high = max over the stacked spaces (wrappers.py:113-123); the control planes are declared
         # Box(0, 1) by the reference (control_wrappers.py:96-104) although target / range can leave that interval
-        if self._n_ctrl_planes:  # control_wrappers.py:96-104: low / high arrays, zeros / ones for the control planes
+        if v.obs_format == "codes":  # tile codes: Box(0, per-channel max), control planes [0, 1] in front
+            high = np.broadcast_to(np.asarray([1.0] * self._n_ctrl_planes + codes_high(v), np.float32), shape)
+            self.observation_space = Box(low=np.zeros(shape, np.float32), high=np.array(high), dtype=np.float32)
+        elif self._n_ctrl_planes:  # control_wrappers.py:96-104: low / high arrays, zeros / ones for the control planes
             self.observation_space = Box(low=np.zeros(shape, np.float32), high=np.ones(shape, np.float32), dtype=np.float32)
         else:
             self.observation_space = Box(low=0, high=1, shape=shape, dtype=np.float32)

@@ -83,12 +83,71 @@ def build_config(problem, representation, map_shape, obs_window=None, weights=No
     return c, spec, obs_window
 
 
+# Observation forms.  "onehot" (default): the reference's image, uint8 [N, OH, OW, C] (wrappers.py:407-437 Cropped ->
+# :232-257 OneHotEncoding -> :140-150 ToImage).  "codes": the same stack without OneHotEncoding, one byte per cell and plane
+# (include/pcgrl_amd_codes.h): narrow / turtle [N, OH, OW, 1 + static_tiles] (0 = outside the map, 1 + tile; the static mask),
+# wide [N, H, W, 1] (tile), 3-D [N, o0, o1, o2, 1] (index of the one-hot channel).  codes_to_onehot() restores the image.
+OBS_FORMATS = ("onehot", "codes")
+_ROLLOUT_SCRATCH_BYTES = 256 << 20  # one-hot scratch of a codes rollout that keeps every step: chunks of steps up to this size
+# codes rollout(want_obs="all"), 2-D: K x (step + encoder) where the one-hot image has more bytes per cell than this, else the
+# one-hot rollout + compress (profiles/obs_codes.json "rollout_all": zelda-turtle, 9 bytes per cell, 10.9 vs 26.4 us per step;
+# sokoban-wide, 5 bytes, 11.2 vs 4.9 -- its one-launch rollout kernel; binary-narrow, 3 bytes, 12.2 vs 12.6)
+_ROLLOUT_COMPRESS_MAX_CHANNELS = 5
+
+
+def _check_obs_format(obs_format):
+    if obs_format not in OBS_FORMATS:
+        raise ValueError(f"obs_format must be one of {OBS_FORMATS}, got {obs_format!r}")
+
+
+def obs_shape_for(cfg, spec, obs_window, obs_format="onehot"):
+    """per-env observation shape of a build_config() result in either form (what pcgrl_obs_shape / pcgrl_codes_shape return)"""
+    _check_obs_format(obs_format)
+    nt, static = spec.n_tiles, 1 if cfg.static_tiles else 0
+    if cfg.ndim == 3:
+        return tuple(obs_window) + ((4,) if obs_format == "onehot" else (1,))
+    if cfg.representation == REPRESENTATIONS["wide"]:
+        return tuple(cfg.dims[i] for i in range(2)) + ((nt,) if obs_format == "onehot" else (1,))
+    return tuple(obs_window) + ((nt + 1 + static,) if obs_format == "onehot" else (1 + static,))
+
+
+def _onehot_channels(problem, representation, map_shape):
+    """one-hot channels plane 0 of the codes expands to"""
+    if len(tuple(map_shape)) == 3:
+        return 4
+    nt = problem_spec(problem, map_shape).n_tiles
+    return nt if representation == "wide" else nt + 1
+
+
+def codes_high(env):
+    """largest value of each codes plane (the observation_space bound): C - 1 for plane 0, 1 for the static plane"""
+    c = _onehot_channels(env.problem, env.representation, env.map_shape)
+    return [c - 1] + [1] * (env.obs_shape[-1] - 1)
+
+
+def codes_to_onehot(codes, env):
+    """The one-hot observation of `codes` (a torch tensor [..., P] in the codes form of `env`, on any device): one_hot(plane
+    0, C) ++ the static plane, uint8 -- bit for bit what the env's "onehot" form shows.  `env`: anything with `problem`,
+    `representation` and `map_shape` (a VecPcgrlEnv, SubBatchedVecEnv, ...).  What a policy's first layer does."""
+    c = _onehot_channels(env.problem, env.representation, env.map_shape)
+    codes = torch.as_tensor(codes)
+    # (== F.one_hot(codes[..., 0].long(), c) without its int64 intermediate)
+    oh = (codes[..., :1] == torch.arange(c, dtype=codes.dtype, device=codes.device)).to(torch.uint8)
+    if codes.shape[-1] > 1:
+        oh = torch.cat((oh, codes[..., 1:].to(torch.uint8)), dim=-1)
+    return oh
+
+
 class VecPcgrlEnv:
     """N independent PCGRL envs on one GPU.
 
     step(actions) -> (obs uint8 [N, *obs_shape], reward f32 [N], done bool [N], truncated bool [N], info)
       info["stats"]  int32 [N, n_stats] in `self.stat_keys` order
     Output tensors are owned by the env and overwritten by the next step()/reset() (clone to keep).
+    obs_format="codes": every call hands out the tile-code form instead of the one-hot image (see OBS_FORMATS; the
+    engine, its state and checkpoints are the same).  2-D: the call runs without a one-hot output and the codes come from
+    the state after it (pcgrl_observe_codes); the 3-D maze, step_ready and rollouts that keep every step: the one-hot into
+    a scratch buffer, then pcgrl_onehot_to_codes.
     auto_reset=True (default): finished envs restart inside the same launch (RLlib's convention: the returned
     observation is the first of the new episode); last_episode() exposes what RLlib's callbacks read at
     episode end (rl/callbacks.py:91-117).
@@ -97,7 +156,8 @@ class VecPcgrlEnv:
     def __init__(self, problem, representation, map_shape, num_envs, device="cuda:0", obs_window=None, weights=None,
                  max_board_scans=3, change_percentage=None, seeds=None, auto_reset=True, solver_power=10000,
                  static_trgs=None, controls=None, reward_dtype=torch.float32, act_window=None, static_prob=None,
-                 n_static_walls=None, static_eval=False, _out=None):
+                 n_static_walls=None, static_eval=False, obs_format="onehot", _out=None):
+        _check_obs_format(obs_format)
         if not torch.cuda.is_available():
             raise RuntimeError("VecPcgrlEnv needs a GPU (ROCm device); there is no CPU fallback in the product path")
         self.device = torch.device(device)
@@ -125,6 +185,14 @@ class VecPcgrlEnv:
         nd = C.c_int32()
         _lib.check(L.pcgrl_obs_shape(h, C.byref(shape), C.byref(nd)), "pcgrl_obs_shape")
         self.obs_shape = tuple(shape[i] for i in range(nd.value))
+        self.obs_format = obs_format
+        self.onehot_shape = self.obs_shape
+        self._codes = obs_format == "codes"
+        self._from_state = self._codes and len(self.map_shape) == 2  # (2-D: codes from the state after the call)
+        if self._codes:
+            _lib.check(L.pcgrl_codes_shape(h, C.byref(shape), C.byref(nd)), "pcgrl_codes_shape")
+            self.obs_shape = tuple(shape[i] for i in range(nd.value))
+            assert self.obs_shape == obs_shape_for(self.cfg, self.spec, self.obs_window, obs_format), self.obs_shape
         n_act = {"narrow": self.spec.n_tiles, "turtle": self.spec.n_tiles + 4,
                  "wide": self.n_cells * self.spec.n_tiles}[representation]
         self.num_actions = n_act
@@ -140,6 +208,10 @@ class VecPcgrlEnv:
             self._done = torch.empty(N, dtype=torch.uint8, device=dev)
             self._stats = torch.empty((N, self.n_stats), dtype=torch.int32, device=dev)
         self._ptrs = (self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._stats.data_ptr())
+        # codes form without a from-state encoder (3-D): the one-hot observation goes here and is compressed
+        self._scratch = None
+        if self._codes and not self._from_state:
+            self._scratch = torch.empty((N,) + self.onehot_shape, dtype=torch.uint8, device=dev)
         # controllable mode / float64 rewards go through pcgrl_step_ex
         self._reward64 = torch.empty(N, dtype=torch.float64, device=dev) if reward_dtype == torch.float64 else None
         self._ctrl_obs = torch.zeros((N, 2 * len(self.controls)), dtype=torch.float32, device=dev) if self.controls else None
@@ -196,7 +268,7 @@ class VecPcgrlEnv:
         _lib.check(self._L.pcgrl_reset(self._h, m.data_ptr() if m is not None else None,
                                        g.data_ptr() if g is not None else None,
                                        p.data_ptr() if p is not None else None, self._stream()), "pcgrl_reset")
-        _lib.check(self._L.pcgrl_observe(self._h, self._ptrs[0], self._stream()), "pcgrl_observe")
+        self._observe_into(self._ptrs[0], self._stream())
         if self._ctrl_obs is not None:
             _lib.check(self._L.pcgrl_ctrl_observe(self._h, self._ctrl_obs.data_ptr(), self._stream()), "pcgrl_ctrl_observe")
             return self._obs, {"ctrl_obs": self._ctrl_obs}
@@ -206,10 +278,37 @@ class VecPcgrlEnv:
         if actions.numel() != self.num_envs * self.action_entries:
             raise ValueError(f"actions must hold {self.num_envs} x {self.action_entries} entries, got {tuple(actions.shape)}")
 
+    # -- the codes form: where a launch writes its one-hot observation, and the codes after it -----------------------
+    def _step_obs_ptr(self, out_ptr):
+        """observation pointer for a launch whose observation is to end up at out_ptr (in this env's form)"""
+        if not self._codes:
+            return out_ptr
+        return None if self._from_state else self._scratch.data_ptr()
+
+    def _codes_after(self, out_ptr, stream):
+        """after a launch given _step_obs_ptr(out_ptr): the codes of its observation into out_ptr"""
+        if self._from_state:
+            rc = self._L.pcgrl_observe_codes(self._h, out_ptr, stream)
+        else:
+            rc = self._L.pcgrl_onehot_to_codes(self._h, self._scratch.data_ptr(), self.num_envs, out_ptr, stream)
+        if rc:
+            _lib.check(rc, "pcgrl_observe_codes / pcgrl_onehot_to_codes")
+
+    def _observe_into(self, out_ptr, stream):
+        """the observation of the current state, in this env's form, into out_ptr"""
+        if self._codes and self._from_state:
+            _lib.check(self._L.pcgrl_observe_codes(self._h, out_ptr, stream), "pcgrl_observe_codes")
+            return
+        _lib.check(self._L.pcgrl_observe(self._h, self._step_obs_ptr(out_ptr), stream), "pcgrl_observe")
+        if self._codes:
+            self._codes_after(out_ptr, stream)
+
     def step(self, actions):
         self._check_action_shape(actions)
         if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if self._codes:
+            return self._step_codes(actions)
         if self._ex:
             rc = self._L.pcgrl_step_ex(
                 self._h, actions.data_ptr(), 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
@@ -220,6 +319,22 @@ class VecPcgrlEnv:
                                     self._ptrs[1], self._ptrs[2], self._ptrs[3], self._stream())
         if rc:
             _lib.check(rc, "pcgrl_step")
+        return self._step_out
+
+    def _step_codes(self, actions):
+        s = self._stream()
+        obs = self._step_obs_ptr(self._ptrs[0])
+        if self._ex:
+            rc = self._L.pcgrl_step_ex(
+                self._h, actions.data_ptr(), 1 if self.auto_reset else 0, obs, self._ptrs[1],
+                self._reward64.data_ptr() if self._reward64 is not None else None, self._ptrs[2], self._ptrs[3],
+                self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None, s)
+        else:
+            rc = self._L.pcgrl_step(self._h, actions.data_ptr(), 1 if self.auto_reset else 0, obs, self._ptrs[1], self._ptrs[2],
+                                    self._ptrs[3], s)
+        if rc:
+            _lib.check(rc, "pcgrl_step")
+        self._codes_after(self._ptrs[0], s)
         return self._step_out
 
     # -- controllable generation (control_wrappers.py:27-121) -----------------------------------------------------
@@ -304,6 +419,14 @@ class VecPcgrlEnv:
             self._status = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
             info = dict(self._step_out[4], status=self._status)
             self._ready_out = self._step_out[:4] + (info,)
+        if self._codes:
+            # asynchronous stepping leaves busy envs' rows as earlier calls wrote them: the one-hot observation is kept in
+            # the scratch (reset / observe / step_ready), and the codes are always those of the whole scratch
+            if self._scratch is None:
+                self._scratch = torch.empty((self.num_envs,) + self.onehot_shape, dtype=torch.uint8, device=self.device)
+            self._from_state = budget <= 0 and len(self.map_shape) == 2
+            if budget > 0:  # (what the last call showed: nobody is busy while there is no budget)
+                _lib.check(self._L.pcgrl_observe(self._h, self._scratch.data_ptr(), self._stream()), "pcgrl_observe")
 
     def step_ready(self, actions):
         """pcgrl_step_ready: like step(), plus info["status"] uint8 [N] = EMITTED (this env completed a step in this launch:
@@ -313,13 +436,15 @@ class VecPcgrlEnv:
         self._check_action_shape(actions)
         if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        rc = self._L.pcgrl_step_ready(self._h, actions.data_ptr(), 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
-                                      self._ptrs[2], self._ptrs[3], self._status.data_ptr(), self._stream())
+        rc = self.step_ready_raw(actions.data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             _lib.check(rc, "pcgrl_step_ready")
         return self._ready_out
 
     def step_ready_raw(self, actions_ptr, status_ptr, stream):
+        if self._codes:  # the one-hot rows into the persistent scratch, then every scratch row converted
+            return self._L.pcgrl_step_ready_codes(self._h, actions_ptr, 1 if self.auto_reset else 0, self._scratch.data_ptr(),
+                                                  self._ptrs[0], self._ptrs[1], self._ptrs[2], self._ptrs[3], status_ptr, stream)
         return self._L.pcgrl_step_ready(self._h, actions_ptr, 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
                                         self._ptrs[2], self._ptrs[3], status_ptr, stream)
 
@@ -331,12 +456,24 @@ class VecPcgrlEnv:
 
     def step_raw(self, actions_ptr, stream):
         """Lowest-overhead launch: device pointer of int32 actions + raw hipStream_t."""
+        if self._codes:
+            rc = self._L.pcgrl_step(self._h, actions_ptr, 1 if self.auto_reset else 0, self._step_obs_ptr(self._ptrs[0]),
+                                    self._ptrs[1], self._ptrs[2], self._ptrs[3], stream)
+            if rc == 0:
+                self._codes_after(self._ptrs[0], stream)
+            return rc
         return self._L.pcgrl_step(self._h, actions_ptr, 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
                                   self._ptrs[2], self._ptrs[3], stream)
 
     def step_seq_raw(self, rows_ptr, row_stride, n_rows, first_row, n_steps, stream):
         """n_steps pcgrl_step launches from ONE foreign call (pcgrl_step_seq): step k uses action row
         (first_row + k) % n_rows of the int32 buffer at rows_ptr (rows row_stride entries apart)."""
+        if self._codes:  # (two launches per step)
+            for k in range(n_steps):
+                rc = self.step_raw(rows_ptr + 4 * ((first_row + k) % n_rows) * row_stride, stream)
+                if rc:
+                    return rc
+            return 0
         return self._L.pcgrl_step_seq(self._h, rows_ptr, row_stride, n_rows, first_row, n_steps, 1 if self.auto_reset else 0,
                                       self._ptrs[0], self._ptrs[1], self._ptrs[2], self._ptrs[3], stream)
 
@@ -352,6 +489,10 @@ class VecPcgrlEnv:
         if actions.numel() != K * self.num_envs * self.action_entries:
             raise ValueError(f"actions must be [K, {self.num_envs}" + (f", {self.action_entries}]" if self.action_entries > 1 else "]"))
         N, dev = self.num_envs, self.device
+        if self._codes:
+            if want_obs not in ("all", "last", "none"):
+                raise ValueError(f"want_obs must be 'all', 'last' or 'none', got {want_obs!r}")
+            return self._rollout_codes(actions, K, want_obs)
         obs = None
         if want_obs == "all":
             obs = torch.empty((K, N) + self.obs_shape, dtype=torch.uint8, device=dev)
@@ -368,6 +509,50 @@ class VecPcgrlEnv:
                                             self._stream()), "pcgrl_rollout_ex")
         return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
 
+    def _rollout_codes(self, actions, K, want_obs):
+        """rollout() in the codes form.  "none": as in the one-hot form.  "last": 2-D -- the rollout without observations, then
+        the codes of the final state; 3-D -- the last one-hot observation into the scratch, compressed.  "all": 2-D images of
+        more than _ROLLOUT_COMPRESS_MAX_CHANNELS bytes per cell -- K x (step launch without an observation + encoder into row
+        k); otherwise the rollout in chunks of steps whose one-hot observations fit a scratch of <= 256 MB (at least one step),
+        each chunk compressed into its rows of the result.  Chunks of one rollout give the results of the whole (pcgrl_rollout's definition: n_steps
+        pcgrl_step calls), and every chunk keeps the engine's rollout form (one launch, two kernels, ...)."""
+        N, dev, s = self.num_envs, self.device, self._stream()
+        rew = torch.empty((K, N), dtype=torch.float32, device=dev)
+        rew64 = torch.empty((K, N), dtype=torch.float64, device=dev) if self._reward64 is not None else None
+        done = torch.empty((K, N), dtype=torch.uint8, device=dev)
+        stats = torch.empty((K, N, self.n_stats), dtype=torch.int32, device=dev)
+        ctrl = self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None
+        L, h, ar = self._L, self._h, 1 if self.auto_reset else 0
+        if want_obs != "all":
+            obs = torch.empty((N,) + self.obs_shape, dtype=torch.uint8, device=dev) if want_obs == "last" else None
+            step_obs = None if obs is None else self._step_obs_ptr(obs.data_ptr())
+            _lib.check(L.pcgrl_rollout_ex(h, actions.data_ptr(), K, ar, step_obs, 1, rew.data_ptr(),
+                                          rew64.data_ptr() if rew64 is not None else None, done.data_ptr(), stats.data_ptr(), ctrl, s),
+                       "pcgrl_rollout_ex")
+            if obs is not None:
+                self._codes_after(obs.data_ptr(), s)
+            return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
+        obs = torch.empty((K, N) + self.obs_shape, dtype=torch.uint8, device=dev)
+        if self._from_state and self.onehot_shape[-1] > _ROLLOUT_COMPRESS_MAX_CHANNELS:
+            act = actions.reshape(K, -1)
+            for k in range(K):  # (pcgrl_rollout's own definition: K pcgrl_step calls)
+                _lib.check(L.pcgrl_step_ex(h, act[k].data_ptr(), ar, None, rew[k].data_ptr(),
+                                           rew64[k].data_ptr() if rew64 is not None else None, done[k].data_ptr(),
+                                           stats[k].data_ptr(), ctrl if k == K - 1 else None, s), "pcgrl_step_ex")
+                self._codes_after(obs[k].data_ptr(), s)
+            return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
+        row_oh = N * int(np.prod(self.onehot_shape))
+        kc = max(1, min(K, _ROLLOUT_SCRATCH_BYTES // row_oh))
+        scratch = torch.empty((kc, N) + self.onehot_shape, dtype=torch.uint8, device=dev)
+        act = actions.reshape(K, -1)
+        for k0 in range(0, K, kc):
+            kk = min(kc, K - k0)
+            _lib.check(L.pcgrl_rollout_ex(h, act[k0].data_ptr(), kk, ar, scratch.data_ptr(), 0, rew[k0].data_ptr(),
+                                          rew64[k0].data_ptr() if rew64 is not None else None, done[k0].data_ptr(), stats[k0].data_ptr(),
+                                          ctrl if k0 + kk == K else None, s), "pcgrl_rollout_ex")
+            _lib.check(L.pcgrl_onehot_to_codes(h, scratch.data_ptr(), kk * N, obs[k0].data_ptr(), s), "pcgrl_onehot_to_codes")
+        return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
+
     @property
     def ctrl_obs(self):
         """float32 [N, 2 * len(controls)]: (target / range, metric / range) per control metric, as of the last step"""
@@ -379,8 +564,11 @@ class VecPcgrlEnv:
         self._check_action_shape(actions)
         if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        _lib.check(self._L.pcgrl_update(self._h, actions.data_ptr(), self._ptrs[0] if want_obs else None, self._stream()),
+        s = self._stream()
+        _lib.check(self._L.pcgrl_update(self._h, actions.data_ptr(), self._step_obs_ptr(self._ptrs[0]) if want_obs else None, s),
                    "pcgrl_update")
+        if want_obs and self._codes:
+            self._codes_after(self._ptrs[0], s)
         return self._obs if want_obs else None
 
     def refresh_stats(self):
@@ -389,7 +577,7 @@ class VecPcgrlEnv:
         return self._stats
 
     def observe(self):
-        _lib.check(self._L.pcgrl_observe(self._h, self._ptrs[0], self._stream()), "pcgrl_observe")
+        self._observe_into(self._ptrs[0], self._stream())
         return self._obs
 
     # -- static tiles (envs/reps/wrappers.py:234-376) ---------------------------------------------------------------
@@ -524,6 +712,7 @@ class SubBatchedVecEnv:
     """
 
     def __init__(self, problem, representation, map_shape, num_envs, sub_batches, device="cuda:0", seeds=None, **kw):
+        _check_obs_format(kw.get("obs_format", "onehot"))
         k = int(sub_batches)
         if k < 1 or num_envs % k:
             raise ValueError("num_envs must be a multiple of sub_batches")
@@ -536,13 +725,7 @@ class SubBatchedVecEnv:
                              kw.get("static_trgs"), kw.get("controls"), kw.get("act_window"), kw.get("static_prob"),
                              kw.get("n_static_walls"), kw.get("static_eval", False))
         cfg, spec, obs_window = probe
-        nt = spec.n_tiles
-        if representation == "wide":
-            obs_shape = tuple(map_shape) + (nt,)
-        elif len(map_shape) == 3:
-            obs_shape = tuple(obs_window) + (4,)
-        else:
-            obs_shape = tuple(obs_window) + (nt + 1 + (1 if cfg.static_tiles else 0),)
+        obs_shape = obs_shape_for(cfg, spec, obs_window, kw.get("obs_format", "onehot"))
         N, dev = self.num_envs, self.device
         self._obs = torch.empty((N,) + obs_shape, dtype=torch.uint8, device=dev)
         self._reward = torch.empty(N, dtype=torch.float32, device=dev)
@@ -557,7 +740,7 @@ class SubBatchedVecEnv:
         e0 = self.envs[0]
         assert e0.obs_shape == obs_shape, (e0.obs_shape, obs_shape)
         for a in ("obs_shape", "num_actions", "action_entries", "stat_keys", "n_stats", "spec", "cfg", "map_shape", "auto_reset",
-                  "problem", "representation"):
+                  "problem", "representation", "obs_format", "onehot_shape"):
             setattr(self, a, getattr(e0, a))
         done = self._done.view(torch.bool)
         self._step_out = (self._obs, self._reward, done, done, {"stats": self._stats})
@@ -702,7 +885,7 @@ class SubBatchedVecEnv:
 def make_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, sub_batches=1):
     """Batched counterpart of control_pcgrl/rl/envs.py:make_env(cfg).  `cfg` is the reference's Config-like
     object (attributes or dict keys): task.problem, task.map_shape, task.obs_window, task.weights,
-    representation, max_board_scans, change_percentage."""
+    representation, max_board_scans, change_percentage; obs_format ("onehot" default, or "codes": VecPcgrlEnv)."""
     unsupported = {
         "n_aux_tiles": _cfg_get(cfg, "n_aux_tiles", 0) or None,
         "show_agents": _cfg_get(cfg, "show_agents", False) or None,
@@ -723,4 +906,4 @@ def make_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, su
         seeds=seeds, auto_reset=auto_reset, controls=_cfg_get(cfg, "controls"),
         reward_dtype=torch.float64 if _cfg_get(cfg, "controls") else torch.float32,
         act_window=_cfg_get(cfg, "act_window"), static_prob=_cfg_get(cfg, "static_prob"),
-        n_static_walls=_cfg_get(cfg, "n_static_walls"))
+        n_static_walls=_cfg_get(cfg, "n_static_walls"), obs_format=_cfg_get(cfg, "obs_format", "onehot") or "onehot")
