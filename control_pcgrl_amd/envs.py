@@ -49,6 +49,22 @@ except Exception:  # pragma: no cover - gymnasium is not in the build image
             return f"MultiDiscrete({self.nvec.tolist()})"
 
 
+def _observation_space(vec, dtype=np.float32):
+    """The adapters' observation space over a VecPcgrlEnv: controllable mode prepends 2 * len(controls) constant planes
+    (control_wrappers.py:86-104, :189-214).  wrappers.py:113-123 ToImage: Box(low=0, high=max over the stacked spaces,
+    shape=(H, W, C)) = Box(0, 1) float32 for the one-hot map; the control planes are declared [0, 1] by the reference too
+    (control_wrappers.py:96-104) although target / range can leave that interval.  Tile codes (obs_format="codes"): Box(0,
+    per-channel max) in `dtype`, control planes [0, 1] in front."""
+    k2 = 2 * len(vec.controls)
+    shape = vec.obs_shape[:-1] + (vec.obs_shape[-1] + k2,)
+    if vec.obs_format == "codes":
+        high = np.broadcast_to(np.asarray([1] * k2 + codes_high(vec), dtype), shape)
+        return Box(low=np.zeros(shape, dtype), high=np.array(high), dtype=dtype)
+    if k2:
+        return Box(low=np.zeros(shape, np.float32), high=np.ones(shape, np.float32), dtype=np.float32)
+    return Box(low=0, high=1, shape=shape, dtype=np.float32)
+
+
 class PcgrlGymEnv:
     """One env with the reference's API on top of the batched engine."""
 
@@ -59,19 +75,8 @@ class PcgrlGymEnv:
                                                               seeds=None if seed is None else [seed])
         assert self._vec.num_envs == 1 and not self._vec.auto_reset
         v = self._vec
-        # wrappers.py:121-123 ToImage: Box(low=0, high=max tile value, shape=(H, W, C)) float32
-        # controllable mode prepends 2 * len(controls) constant planes (control_wrappers.py:86-104, :189-214)
         self._n_ctrl_planes = 2 * len(v.controls)
-        shape = v.obs_shape[:-1] + (v.obs_shape[-1] + self._n_ctrl_planes,)
-        # ToImage takes high = max over the stacked spaces (wrappers.py:113-123); the control planes are declared
-        # Box(0, 1) by the reference (control_wrappers.py:96-104) although target / range can leave that interval
-        if v.obs_format == "codes":  # tile codes: Box(0, per-channel max), control planes [0, 1] in front
-            high = np.broadcast_to(np.asarray([1.0] * self._n_ctrl_planes + codes_high(v), np.float32), shape)
-            self.observation_space = Box(low=np.zeros(shape, np.float32), high=np.array(high), dtype=np.float32)
-        elif self._n_ctrl_planes:  # control_wrappers.py:96-104: low / high arrays, zeros / ones for the control planes
-            self.observation_space = Box(low=np.zeros(shape, np.float32), high=np.ones(shape, np.float32), dtype=np.float32)
-        else:
-            self.observation_space = Box(low=0, high=1, shape=shape, dtype=np.float32)
+        self.observation_space = _observation_space(v)
         if v.act_window:  # envs/reps/wrappers.py:434-439: one tile id per cell of the action patch
             self.action_space = MultiDiscrete([v.spec.n_tiles] * v.action_entries)
         else:

@@ -35,8 +35,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .envs import Box, Discrete, MultiDiscrete
-from .vec_env import VecPcgrlEnv, codes_high, make_vec_env
+from .envs import Discrete, MultiDiscrete, _observation_space
+from .vec_env import VecPcgrlEnv, make_vec_env
 
 try:  # pragma: no cover - ray is not in the build image
     from ray.rllib.env.vector_env import VectorEnv as _Base
@@ -132,16 +132,8 @@ class PcgrlVectorEnv(_Base):
         self.obs_dtype = np.dtype(obs_dtype if not self.n_ctrl_planes else np.float32)  # (control planes are fractions)
         if self.obs_dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
             raise ValueError("obs_dtype must be float32 (the reference's declared Box dtype) or uint8 (the engine's bytes)")
-        shape = v.obs_shape[:-1] + (v.obs_shape[-1] + self.n_ctrl_planes,)
-        # wrappers.py:113-123 ToImage: Box(0, max over the stacked spaces) = Box(0, 1) for the one-hot map; the control
-        # planes are declared [0, 1] by the reference too (control_wrappers.py:96-104) although metric / range may exceed it
-        if v.obs_format == "codes":  # tile codes (obs_format="codes"): Box(0, per-channel max) in the dtype handed out
-            high = np.broadcast_to(np.asarray([1] * self.n_ctrl_planes + codes_high(v), self.obs_dtype), shape)
-            self.observation_space = Box(low=np.zeros(shape, self.obs_dtype), high=np.array(high), dtype=self.obs_dtype)
-        elif self.n_ctrl_planes:
-            self.observation_space = Box(low=np.zeros(shape, np.float32), high=np.ones(shape, np.float32), dtype=np.float32)
-        else:
-            self.observation_space = Box(low=0, high=1, shape=shape, dtype=np.float32)
+        self.observation_space = _observation_space(v, self.obs_dtype)
+        shape = self.observation_space.shape
         self.action_space = (MultiDiscrete([v.spec.n_tiles] * v.action_entries) if v.act_window
                              else Discrete(v.num_actions))
         if _Base is not object:  # pragma: no cover
@@ -276,14 +268,10 @@ class PcgrlVectorEnv(_Base):
         v = self.vec
         m = torch.as_tensor(mask.astype(np.uint8), device=v.device)
         L, s = v._L, v._stream()
-        from . import _lib
         lease = self._lease()
         obs_p, _, stats_p, _, ctrl_p = self._out_ptrs(lease)
         _lib.check(L.pcgrl_reset(v._h, m.data_ptr(), None, None, s), "pcgrl_reset")
-        if v.obs_format == "codes":
-            v._observe_into(obs_p, s)
-        else:
-            _lib.check(L.pcgrl_observe(v._h, obs_p, s), "pcgrl_observe")
+        _lib.check(v.observe_into(obs_p, s), "pcgrl_observe")
         _lib.check(L.pcgrl_get_state(v._h, None, None, None, stats_p, None, None, s), "pcgrl_get_state")
         if self.n_ctrl_planes:
             _lib.check(L.pcgrl_ctrl_observe(v._h, ctrl_p, s), "pcgrl_ctrl_observe")
@@ -332,16 +320,9 @@ class PcgrlVectorEnv(_Base):
             self._act_dev.copy_(self._act, non_blocking=True)
         lease = self._lease()
         obs_p, rew_p, stats_p, done_p, ctrl_p = self._out_ptrs(lease)
-        step_obs = v._step_obs_ptr(obs_p)  # (codes form: none, or the scratch; the codes follow the launch)
-        if self.n_ctrl_planes:
-            rc = v._L.pcgrl_step_ex(v._h, self._act_dev.data_ptr(), 0, step_obs, rew_p, None, done_p, stats_p, ctrl_p, s)
-        else:
-            rc = v._L.pcgrl_step(v._h, self._act_dev.data_ptr(), 0, step_obs, rew_p, done_p, stats_p, s)
+        rc = v.step_into(self._act_dev.data_ptr(), obs_p, rew_p, None, done_p, stats_p, ctrl_p if self.n_ctrl_planes else None, s)
         if rc:
-            from . import _lib
             _lib.check(rc, "pcgrl_step")
-        if v.obs_format == "codes":
-            v._codes_after(obs_p, s)
         self._finish(lease, s)  # the one device -> host copy of the call
         r = self._views(lease)
         self._stats[...] = r["stats"]

@@ -6,6 +6,7 @@ PCGRLWrapper(PcgrlCtrlEnv))  stack (control_pcgrl/rl/envs.py:28-81): same observ
 env's GPU; step() performs no host synchronisation.
 """
 import ctypes as C
+import inspect
 from types import SimpleNamespace
 
 import numpy as np
@@ -83,6 +84,9 @@ def build_config(problem, representation, map_shape, obs_window=None, weights=No
     return c, spec, obs_window
 
 
+_CONFIG_ARGS = tuple(inspect.signature(build_config).parameters)[3:]  # (the keyword arguments VecPcgrlEnv hands to build_config)
+
+
 # Observation forms.  "onehot" (default): the reference's image, uint8 [N, OH, OW, C] (wrappers.py:407-437 Cropped ->
 # :232-257 OneHotEncoding -> :140-150 ToImage).  "codes": the same stack without OneHotEncoding, one byte per cell and plane
 # (include/pcgrl_amd_codes.h): narrow / turtle [N, OH, OW, 1 + static_tiles] (0 = outside the map, 1 + tile; the static mask),
@@ -138,6 +142,15 @@ def codes_to_onehot(codes, env):
     return oh
 
 
+# what follows a launch in the codes form (VecPcgrlEnv._route_obs): the codes of its observation into out_ptr
+def _codes_from_state(env, out_ptr, stream):
+    return env._L.pcgrl_observe_codes(env._h, out_ptr, stream)
+
+
+def _codes_from_scratch(env, out_ptr, stream):
+    return env._L.pcgrl_onehot_to_codes(env._h, env._via, env.num_envs, out_ptr, stream)
+
+
 class VecPcgrlEnv:
     """N independent PCGRL envs on one GPU.
 
@@ -187,9 +200,7 @@ class VecPcgrlEnv:
         self.obs_shape = tuple(shape[i] for i in range(nd.value))
         self.obs_format = obs_format
         self.onehot_shape = self.obs_shape
-        self._codes = obs_format == "codes"
-        self._from_state = self._codes and len(self.map_shape) == 2  # (2-D: codes from the state after the call)
-        if self._codes:
+        if obs_format == "codes":
             _lib.check(L.pcgrl_codes_shape(h, C.byref(shape), C.byref(nd)), "pcgrl_codes_shape")
             self.obs_shape = tuple(shape[i] for i in range(nd.value))
             assert self.obs_shape == obs_shape_for(self.cfg, self.spec, self.obs_window, obs_format), self.obs_shape
@@ -208,10 +219,8 @@ class VecPcgrlEnv:
             self._done = torch.empty(N, dtype=torch.uint8, device=dev)
             self._stats = torch.empty((N, self.n_stats), dtype=torch.int32, device=dev)
         self._ptrs = (self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._stats.data_ptr())
-        # codes form without a from-state encoder (3-D): the one-hot observation goes here and is compressed
-        self._scratch = None
-        if self._codes and not self._from_state:
-            self._scratch = torch.empty((N,) + self.onehot_shape, dtype=torch.uint8, device=dev)
+        self._scratch = self._status = None  # (the one-hot scratch of the codes form, step_ready's status)
+        self._route_obs()
         # controllable mode / float64 rewards go through pcgrl_step_ex
         self._reward64 = torch.empty(N, dtype=torch.float64, device=dev) if reward_dtype == torch.float64 else None
         self._ctrl_obs = torch.zeros((N, 2 * len(self.controls)), dtype=torch.float32, device=dev) if self.controls else None
@@ -268,73 +277,76 @@ class VecPcgrlEnv:
         _lib.check(self._L.pcgrl_reset(self._h, m.data_ptr() if m is not None else None,
                                        g.data_ptr() if g is not None else None,
                                        p.data_ptr() if p is not None else None, self._stream()), "pcgrl_reset")
-        self._observe_into(self._ptrs[0], self._stream())
+        _lib.check(self.observe_into(self._ptrs[0], self._stream()), "pcgrl_observe")
         if self._ctrl_obs is not None:
             _lib.check(self._L.pcgrl_ctrl_observe(self._h, self._ctrl_obs.data_ptr(), self._stream()), "pcgrl_ctrl_observe")
             return self._obs, {"ctrl_obs": self._ctrl_obs}
         return self._obs, {}
 
-    def _check_action_shape(self, actions):
-        if actions.numel() != self.num_envs * self.action_entries:
-            raise ValueError(f"actions must hold {self.num_envs} x {self.action_entries} entries, got {tuple(actions.shape)}")
-
-    # -- the codes form: where a launch writes its one-hot observation, and the codes after it -----------------------
-    def _step_obs_ptr(self, out_ptr):
-        """observation pointer for a launch whose observation is to end up at out_ptr (in this env's form)"""
-        if not self._codes:
-            return out_ptr
-        return None if self._from_state else self._scratch.data_ptr()
-
-    def _codes_after(self, out_ptr, stream):
-        """after a launch given _step_obs_ptr(out_ptr): the codes of its observation into out_ptr"""
-        if self._from_state:
-            rc = self._L.pcgrl_observe_codes(self._h, out_ptr, stream)
-        else:
-            rc = self._L.pcgrl_onehot_to_codes(self._h, self._scratch.data_ptr(), self.num_envs, out_ptr, stream)
-        if rc:
-            _lib.check(rc, "pcgrl_observe_codes / pcgrl_onehot_to_codes")
-
-    def _observe_into(self, out_ptr, stream):
-        """the observation of the current state, in this env's form, into out_ptr"""
-        if self._codes and self._from_state:
-            _lib.check(self._L.pcgrl_observe_codes(self._h, out_ptr, stream), "pcgrl_observe_codes")
-            return
-        _lib.check(self._L.pcgrl_observe(self._h, self._step_obs_ptr(out_ptr), stream), "pcgrl_observe")
-        if self._codes:
-            self._codes_after(out_ptr, stream)
-
-    def step(self, actions):
-        self._check_action_shape(actions)
+    def _actions(self, actions, steps=None):
+        """`actions` as the engine reads them: int32, contiguous, on the env's device, [steps x] num_envs x action_entries"""
+        if actions.numel() != self.num_envs * self.action_entries * (1 if steps is None else steps):
+            shape = ([steps] if steps is not None else []) + [self.num_envs] + ([self.action_entries] if self.action_entries > 1 else [])
+            raise ValueError(f"actions must be {shape}, got {tuple(actions.shape)}")
         if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        if self._codes:
-            return self._step_codes(actions)
-        if self._ex:
-            rc = self._L.pcgrl_step_ex(
-                self._h, actions.data_ptr(), 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
-                self._reward64.data_ptr() if self._reward64 is not None else None, self._ptrs[2], self._ptrs[3],
-                self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None, self._stream())
-        else:
-            rc = self._L.pcgrl_step(self._h, actions.data_ptr(), 1 if self.auto_reset else 0, self._ptrs[0],
-                                    self._ptrs[1], self._ptrs[2], self._ptrs[3], self._stream())
-        if rc:
-            _lib.check(rc, "pcgrl_step")
-        return self._step_out
+        return actions
 
-    def _step_codes(self, actions):
-        s = self._stream()
-        obs = self._step_obs_ptr(self._ptrs[0])
-        if self._ex:
-            rc = self._L.pcgrl_step_ex(
-                self._h, actions.data_ptr(), 1 if self.auto_reset else 0, obs, self._ptrs[1],
-                self._reward64.data_ptr() if self._reward64 is not None else None, self._ptrs[2], self._ptrs[3],
-                self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None, s)
+    # -- the observation form: where a launch writes its observation, and what follows the launch ---------------------
+    def _route_obs(self, budget=0):
+        """Decides, for this env's form and solver budget, where a launch writes its observation and what then runs
+        (_then) so that the observation arrives at the caller's pointer:
+          one-hot                     the caller's buffer, nothing after
+          codes from the state        no one-hot output, then pcgrl_observe_codes (2-D without a solver budget)
+          codes through the scratch   the one-hot scratch, then pcgrl_onehot_to_codes of every row: the 3-D maze, whose
+                                      observation shows the overlay of the previous statistics update, and asynchronous
+                                      stepping, where the scratch keeps the rows of busy envs"""
+        codes = self.obs_format == "codes"
+        via_scratch = codes and (len(self.map_shape) == 3 or budget > 0)
+        if via_scratch and self._scratch is None:
+            self._scratch = torch.empty((self.num_envs,) + self.onehot_shape, dtype=torch.uint8, device=self.device)
+        self._via = self._scratch.data_ptr() if via_scratch else None  # where launches write when _then follows them
+        self._then = (_codes_from_scratch if via_scratch else _codes_from_state) if codes else None
+        self._step_obs = self._ptrs[0] if self._then is None else self._via
+        if via_scratch and budget > 0:  # the scratch starts as what the last call showed (nobody is busy without a budget)
+            _lib.check(self._L.pcgrl_observe(self._h, self._via, self._stream()), "pcgrl_observe")
+
+    def observe_into(self, obs_ptr, stream):
+        """pcgrl_observe into a caller-given device (or mapped host) buffer, in this env's form; returns the status code"""
+        then = self._then
+        target = obs_ptr if then is None else self._via
+        rc = self._L.pcgrl_observe(self._h, target, stream) if target is not None else 0
+        if rc == 0 and then is not None:
+            rc = then(self, obs_ptr, stream)
+        return rc
+
+    def step_into(self, actions_ptr, obs_ptr, reward_ptr, reward64_ptr, done_ptr, stats_ptr, ctrl_obs_ptr, stream):
+        """One step launch into caller-given device (or mapped host) buffers, the observation in this env's form
+        (pcgrl_step, or pcgrl_step_ex with float64 rewards or the control observation); returns the status code"""
+        then, ar = self._then, 1 if self.auto_reset else 0
+        obs = obs_ptr if then is None else self._via
+        if reward64_ptr is None and ctrl_obs_ptr is None:
+            rc = self._L.pcgrl_step(self._h, actions_ptr, ar, obs, reward_ptr, done_ptr, stats_ptr, stream)
         else:
-            rc = self._L.pcgrl_step(self._h, actions.data_ptr(), 1 if self.auto_reset else 0, obs, self._ptrs[1], self._ptrs[2],
-                                    self._ptrs[3], s)
+            rc = self._L.pcgrl_step_ex(self._h, actions_ptr, ar, obs, reward_ptr, reward64_ptr, done_ptr, stats_ptr, ctrl_obs_ptr,
+                                       stream)
+        if rc == 0 and then is not None:
+            rc = then(self, obs_ptr, stream)
+        return rc
+
+    def step(self, actions):
+        # (the launch of step_into, inline: this call's host cost is what a policy-in-the-loop step pays per call)
+        a, s, p = self._actions(actions).data_ptr(), self._stream(), self._ptrs
+        if self._ex:
+            rc = self._L.pcgrl_step_ex(self._h, a, 1 if self.auto_reset else 0, self._step_obs, p[1],
+                                       self._reward64.data_ptr() if self._reward64 is not None else None, p[2], p[3],
+                                       self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None, s)
+        else:
+            rc = self._L.pcgrl_step(self._h, a, 1 if self.auto_reset else 0, self._step_obs, p[1], p[2], p[3], s)
+        if rc == 0 and self._then is not None:
+            rc = self._then(self, p[0], s)
         if rc:
             _lib.check(rc, "pcgrl_step")
-        self._codes_after(self._ptrs[0], s)
         return self._step_out
 
     # -- controllable generation (control_wrappers.py:27-121) -----------------------------------------------------
@@ -374,8 +386,8 @@ class VecPcgrlEnv:
     def set_target_resampling(self, enable=True, seed=0):
         """UniformNoiseyTargets on the device (control_wrappers.py:442-471): from each env's next reset on -- explicit or
         automatic, also inside a captured HIP graph -- every control target is drawn ~ U(cond_bounds) from the env's own
-        counter-based stream (pcgrl_set_target_resampling) and replaces whatever was queued.  `resampled_target` below
-        restates the draw on the host."""
+        counter-based stream (pcgrl_set_target_resampling) and replaces whatever was queued.  The draw is trg_resampled
+        (csrc/pcgrl_kernels2d.h)."""
         if not self.controls:
             raise ValueError("this env was built without `controls`")
         lo = np.array([self.spec.cond_bounds[k][0] for k in self.controls], dtype=np.float64)
@@ -415,38 +427,32 @@ class VecPcgrlEnv:
         finish; step with step_ready() from here on (step() / rollout() / update() are refused).  0: synchronous again.
         In the reference a slow _run_game (sokoban_prob.py:99-148) stalls one env, not the fleet (rl/utils.py:412-415)."""
         _lib.check(self._L.pcgrl_set_solver_budget(self._h, int(budget)), "pcgrl_set_solver_budget")
-        if budget > 0 and getattr(self, "_status", None) is None:
+        if budget > 0 and self._status is None:
             self._status = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
             info = dict(self._step_out[4], status=self._status)
             self._ready_out = self._step_out[:4] + (info,)
-        if self._codes:
-            # asynchronous stepping leaves busy envs' rows as earlier calls wrote them: the one-hot observation is kept in
-            # the scratch (reset / observe / step_ready), and the codes are always those of the whole scratch
-            if self._scratch is None:
-                self._scratch = torch.empty((self.num_envs,) + self.onehot_shape, dtype=torch.uint8, device=self.device)
-            self._from_state = budget <= 0 and len(self.map_shape) == 2
-            if budget > 0:  # (what the last call showed: nobody is busy while there is no budget)
-                _lib.check(self._L.pcgrl_observe(self._h, self._scratch.data_ptr(), self._stream()), "pcgrl_observe")
+        self._route_obs(budget)
 
     def step_ready(self, actions):
         """pcgrl_step_ready: like step(), plus info["status"] uint8 [N] = EMITTED (this env completed a step in this launch:
         its reward / done / stats / obs rows are valid) | BUSY (a search of its level is parked: it ignores the NEXT call's
         action).  An env consumes the action of a call iff it was not busy after the previous one; an emitted transition
-        belongs to the last action the env consumed.  Rows of envs that did not emit keep their previous contents."""
-        self._check_action_shape(actions)
-        if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        rc = self.step_ready_raw(actions.data_ptr(), self._status.data_ptr(), self._stream())
+        belongs to the last action the env consumed.  The reward / done / stats rows of envs that did not emit keep their
+        previous contents; their obs rows are rewritten with the observation of the step in flight."""
+        if self._status is None:
+            raise ValueError("step_ready needs a solver budget: call set_solver_budget(budget > 0) first")
+        rc = self.step_ready_raw(self._actions(actions).data_ptr(), self._status.data_ptr(), self._stream())
         if rc:
             _lib.check(rc, "pcgrl_step_ready")
         return self._ready_out
 
     def step_ready_raw(self, actions_ptr, status_ptr, stream):
-        if self._codes:  # the one-hot rows into the persistent scratch, then every scratch row converted
-            return self._L.pcgrl_step_ready_codes(self._h, actions_ptr, 1 if self.auto_reset else 0, self._scratch.data_ptr(),
-                                                  self._ptrs[0], self._ptrs[1], self._ptrs[2], self._ptrs[3], status_ptr, stream)
-        return self._L.pcgrl_step_ready(self._h, actions_ptr, 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
-                                        self._ptrs[2], self._ptrs[3], status_ptr, stream)
+        p = self._ptrs
+        rc = self._L.pcgrl_step_ready(self._h, actions_ptr, 1 if self.auto_reset else 0, self._step_obs, p[1], p[2], p[3],
+                                      status_ptr, stream)
+        if rc == 0 and self._then is not None:
+            rc = self._then(self, p[0], stream)
+        return rc
 
     def env_busy(self):
         """uint8 [N]: 1 = the env waits for a parked search (after reset(): which envs will ignore the first action)"""
@@ -456,19 +462,16 @@ class VecPcgrlEnv:
 
     def step_raw(self, actions_ptr, stream):
         """Lowest-overhead launch: device pointer of int32 actions + raw hipStream_t."""
-        if self._codes:
-            rc = self._L.pcgrl_step(self._h, actions_ptr, 1 if self.auto_reset else 0, self._step_obs_ptr(self._ptrs[0]),
-                                    self._ptrs[1], self._ptrs[2], self._ptrs[3], stream)
-            if rc == 0:
-                self._codes_after(self._ptrs[0], stream)
-            return rc
-        return self._L.pcgrl_step(self._h, actions_ptr, 1 if self.auto_reset else 0, self._ptrs[0], self._ptrs[1],
-                                  self._ptrs[2], self._ptrs[3], stream)
+        p = self._ptrs
+        rc = self._L.pcgrl_step(self._h, actions_ptr, 1 if self.auto_reset else 0, self._step_obs, p[1], p[2], p[3], stream)
+        if rc == 0 and self._then is not None:
+            rc = self._then(self, p[0], stream)
+        return rc
 
     def step_seq_raw(self, rows_ptr, row_stride, n_rows, first_row, n_steps, stream):
         """n_steps pcgrl_step launches from ONE foreign call (pcgrl_step_seq): step k uses action row
         (first_row + k) % n_rows of the int32 buffer at rows_ptr (rows row_stride entries apart)."""
-        if self._codes:  # (two launches per step)
+        if self._then is not None:  # (a launch follows every step: two launches per step)
             for k in range(n_steps):
                 rc = self.step_raw(rows_ptr + 4 * ((first_row + k) % n_rows) * row_stride, stream)
                 if rc:
@@ -482,76 +485,49 @@ class VecPcgrlEnv:
         launch (pcgrl_rollout / pcgrl_rollout_ex).  Returns (obs, reward [K, N], done [K, N], stats [K, N, n_stats]); obs
         is [K, N, ...] for want_obs="all", [N, ...] (after the last step) for "last", None for "none".  Fresh tensors, not
         the env's step buffers.  Controllable mode: rewards are float64 and `self.ctrl_obs` holds the control observation
-        after the last step."""
+        after the last step.
+        In the codes form, "last" and "none" take the launch path of step(); "all" either runs K x (step launch without an
+        observation + encoder into row k), for 2-D images of more than _ROLLOUT_COMPRESS_MAX_CHANNELS bytes per cell, or
+        the rollout in chunks of steps whose one-hot observations fit a scratch of <= _ROLLOUT_SCRATCH_BYTES (at least one
+        step), each chunk compressed into its rows of the result.  Chunks of one rollout give the results of the whole
+        (pcgrl_rollout's definition: n_steps pcgrl_step calls), and every chunk keeps the engine's rollout form."""
+        if want_obs not in ("all", "last", "none"):
+            raise ValueError(f"want_obs must be 'all', 'last' or 'none', got {want_obs!r}")
         K = int(actions.shape[0])
-        if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        if actions.numel() != K * self.num_envs * self.action_entries:
-            raise ValueError(f"actions must be [K, {self.num_envs}" + (f", {self.action_entries}]" if self.action_entries > 1 else "]"))
-        N, dev = self.num_envs, self.device
-        if self._codes:
-            if want_obs not in ("all", "last", "none"):
-                raise ValueError(f"want_obs must be 'all', 'last' or 'none', got {want_obs!r}")
-            return self._rollout_codes(actions, K, want_obs)
-        obs = None
-        if want_obs == "all":
-            obs = torch.empty((K, N) + self.obs_shape, dtype=torch.uint8, device=dev)
-        elif want_obs == "last":
-            obs = torch.empty((N,) + self.obs_shape, dtype=torch.uint8, device=dev)
-        rew = torch.empty((K, N), dtype=torch.float32, device=dev)
-        rew64 = torch.empty((K, N), dtype=torch.float64, device=dev) if self._reward64 is not None else None
-        done = torch.empty((K, N), dtype=torch.uint8, device=dev)
-        stats = torch.empty((K, N, self.n_stats), dtype=torch.int32, device=dev)
-        _lib.check(self._L.pcgrl_rollout_ex(self._h, actions.data_ptr(), K, 1 if self.auto_reset else 0,
-                                            obs.data_ptr() if obs is not None else None, 1 if want_obs == "last" else 0,
-                                            rew.data_ptr(), rew64.data_ptr() if rew64 is not None else None, done.data_ptr(),
-                                            stats.data_ptr(), self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None,
-                                            self._stream()), "pcgrl_rollout_ex")
-        return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
-
-    def _rollout_codes(self, actions, K, want_obs):
-        """rollout() in the codes form.  "none": as in the one-hot form.  "last": 2-D -- the rollout without observations, then
-        the codes of the final state; 3-D -- the last one-hot observation into the scratch, compressed.  "all": 2-D images of
-        more than _ROLLOUT_COMPRESS_MAX_CHANNELS bytes per cell -- K x (step launch without an observation + encoder into row
-        k); otherwise the rollout in chunks of steps whose one-hot observations fit a scratch of <= 256 MB (at least one step),
-        each chunk compressed into its rows of the result.  Chunks of one rollout give the results of the whole (pcgrl_rollout's definition: n_steps
-        pcgrl_step calls), and every chunk keeps the engine's rollout form (one launch, two kernels, ...)."""
+        actions = self._actions(actions, K)
         N, dev, s = self.num_envs, self.device, self._stream()
+        obs = None if want_obs == "none" else torch.empty(((K, N) if want_obs == "all" else (N,)) + self.obs_shape,
+                                                          dtype=torch.uint8, device=dev)
         rew = torch.empty((K, N), dtype=torch.float32, device=dev)
         rew64 = torch.empty((K, N), dtype=torch.float64, device=dev) if self._reward64 is not None else None
         done = torch.empty((K, N), dtype=torch.uint8, device=dev)
         stats = torch.empty((K, N, self.n_stats), dtype=torch.int32, device=dev)
         ctrl = self._ctrl_obs.data_ptr() if self._ctrl_obs is not None else None
-        L, h, ar = self._L, self._h, 1 if self.auto_reset else 0
-        if want_obs != "all":
-            obs = torch.empty((N,) + self.obs_shape, dtype=torch.uint8, device=dev) if want_obs == "last" else None
-            step_obs = None if obs is None else self._step_obs_ptr(obs.data_ptr())
-            _lib.check(L.pcgrl_rollout_ex(h, actions.data_ptr(), K, ar, step_obs, 1, rew.data_ptr(),
-                                          rew64.data_ptr() if rew64 is not None else None, done.data_ptr(), stats.data_ptr(), ctrl, s),
-                       "pcgrl_rollout_ex")
-            if obs is not None:
-                self._codes_after(obs.data_ptr(), s)
-            return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
-        obs = torch.empty((K, N) + self.obs_shape, dtype=torch.uint8, device=dev)
-        if self._from_state and self.onehot_shape[-1] > _ROLLOUT_COMPRESS_MAX_CHANNELS:
-            act = actions.reshape(K, -1)
+        out = obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
+
+        def rows(k):  # pointers of the outputs from step k on
+            return rew[k].data_ptr(), None if rew64 is None else rew64[k].data_ptr(), done[k].data_ptr(), stats[k].data_ptr()
+
+        L, h, ar, act = self._L, self._h, 1 if self.auto_reset else 0, actions.reshape(K, -1)
+        if want_obs == "all" and self._then is _codes_from_state and self.onehot_shape[-1] > _ROLLOUT_COMPRESS_MAX_CHANNELS:
             for k in range(K):  # (pcgrl_rollout's own definition: K pcgrl_step calls)
-                _lib.check(L.pcgrl_step_ex(h, act[k].data_ptr(), ar, None, rew[k].data_ptr(),
-                                           rew64[k].data_ptr() if rew64 is not None else None, done[k].data_ptr(),
-                                           stats[k].data_ptr(), ctrl if k == K - 1 else None, s), "pcgrl_step_ex")
-                self._codes_after(obs[k].data_ptr(), s)
-            return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
-        row_oh = N * int(np.prod(self.onehot_shape))
-        kc = max(1, min(K, _ROLLOUT_SCRATCH_BYTES // row_oh))
-        scratch = torch.empty((kc, N) + self.onehot_shape, dtype=torch.uint8, device=dev)
-        act = actions.reshape(K, -1)
-        for k0 in range(0, K, kc):
-            kk = min(kc, K - k0)
-            _lib.check(L.pcgrl_rollout_ex(h, act[k0].data_ptr(), kk, ar, scratch.data_ptr(), 0, rew[k0].data_ptr(),
-                                          rew64[k0].data_ptr() if rew64 is not None else None, done[k0].data_ptr(), stats[k0].data_ptr(),
-                                          ctrl if k0 + kk == K else None, s), "pcgrl_rollout_ex")
-            _lib.check(L.pcgrl_onehot_to_codes(h, scratch.data_ptr(), kk * N, obs[k0].data_ptr(), s), "pcgrl_onehot_to_codes")
-        return obs, (rew64 if rew64 is not None else rew), done.view(torch.bool), stats
+                _lib.check(self.step_into(act[k].data_ptr(), obs[k].data_ptr(), *rows(k), ctrl if k == K - 1 else None, s),
+                           "pcgrl_step_ex")
+        elif want_obs == "all" and self._then is not None:
+            kc = max(1, min(K, _ROLLOUT_SCRATCH_BYTES // (N * int(np.prod(self.onehot_shape)))))
+            scratch = torch.empty((kc, N) + self.onehot_shape, dtype=torch.uint8, device=dev)
+            for k0 in range(0, K, kc):
+                kk = min(kc, K - k0)
+                _lib.check(L.pcgrl_rollout_ex(h, act[k0].data_ptr(), kk, ar, scratch.data_ptr(), 0, *rows(k0),
+                                              ctrl if k0 + kk == K else None, s), "pcgrl_rollout_ex")
+                _lib.check(L.pcgrl_onehot_to_codes(h, scratch.data_ptr(), kk * N, obs[k0].data_ptr(), s), "pcgrl_onehot_to_codes")
+        else:
+            target = None if obs is None else obs.data_ptr() if self._then is None else self._via
+            rc = L.pcgrl_rollout_ex(h, actions.data_ptr(), K, ar, target, 1 if want_obs == "last" else 0, *rows(0), ctrl, s)
+            if rc == 0 and obs is not None and self._then is not None:
+                rc = self._then(self, obs.data_ptr(), s)
+            _lib.check(rc, "pcgrl_rollout_ex")
+        return out
 
     @property
     def ctrl_obs(self):
@@ -561,14 +537,11 @@ class VecPcgrlEnv:
     # -- evolution-driver pattern (evo/evolve.py:1083-1120): rep.update() many times, get_stats() once ---------------
     def update(self, actions, want_obs=True):
         """rep.update(action) for every env (+ observation); counters / stats / reward are untouched."""
-        self._check_action_shape(actions)
-        if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        s = self._stream()
-        _lib.check(self._L.pcgrl_update(self._h, actions.data_ptr(), self._step_obs_ptr(self._ptrs[0]) if want_obs else None, s),
-                   "pcgrl_update")
-        if want_obs and self._codes:
-            self._codes_after(self._ptrs[0], s)
+        a, s = self._actions(actions).data_ptr(), self._stream()
+        rc = self._L.pcgrl_update(self._h, a, self._step_obs if want_obs else None, s)
+        if rc == 0 and want_obs and self._then is not None:
+            rc = self._then(self, self._ptrs[0], s)
+        _lib.check(rc, "pcgrl_update")
         return self._obs if want_obs else None
 
     def refresh_stats(self):
@@ -577,7 +550,7 @@ class VecPcgrlEnv:
         return self._stats
 
     def observe(self):
-        self._observe_into(self._ptrs[0], self._stream())
+        _lib.check(self.observe_into(self._ptrs[0], self._stream()), "pcgrl_observe")
         return self._obs
 
     # -- static tiles (envs/reps/wrappers.py:234-376) ---------------------------------------------------------------
@@ -712,7 +685,6 @@ class SubBatchedVecEnv:
     """
 
     def __init__(self, problem, representation, map_shape, num_envs, sub_batches, device="cuda:0", seeds=None, **kw):
-        _check_obs_format(kw.get("obs_format", "onehot"))
         k = int(sub_batches)
         if k < 1 or num_envs % k:
             raise ValueError("num_envs must be a multiple of sub_batches")
@@ -720,11 +692,7 @@ class SubBatchedVecEnv:
         self.device = torch.device(device)
         seeds = np.arange(num_envs) if seeds is None else np.broadcast_to(np.asarray(seeds), (num_envs,))
         n = self.n_sub
-        probe = build_config(problem, representation, map_shape, kw.get("obs_window"), kw.get("weights"),
-                             kw.get("max_board_scans", 3), kw.get("change_percentage"), kw.get("solver_power", 10000),
-                             kw.get("static_trgs"), kw.get("controls"), kw.get("act_window"), kw.get("static_prob"),
-                             kw.get("n_static_walls"), kw.get("static_eval", False))
-        cfg, spec, obs_window = probe
+        cfg, spec, obs_window = build_config(problem, representation, map_shape, **{a: kw[a] for a in _CONFIG_ARGS if a in kw})
         obs_shape = obs_shape_for(cfg, spec, obs_window, kw.get("obs_format", "onehot"))
         N, dev = self.num_envs, self.device
         self._obs = torch.empty((N,) + obs_shape, dtype=torch.uint8, device=dev)
@@ -758,13 +726,19 @@ class SubBatchedVecEnv:
         for j in (range(self.k) if i is None else (i,)):
             cur.wait_stream(self.streams[j])
 
-    def reset(self, **kw):
-        n = self.n_sub
+    def _each(self, call):
+        """[call(i, envs[i]) for every sub-batch i], each on its sub-batch's stream -- ordered after the work queued on the
+        current stream and on that stream (a step_async in flight) -- then joined back into the current stream"""
+        out = []
         for i, e in enumerate(self.envs):
             self._fork(i)
             with torch.cuda.stream(self.streams[i]):
-                e.reset(**{key: (None if v is None else torch.as_tensor(v)[i * n:(i + 1) * n]) for key, v in kw.items()})
+                out.append(call(i, e))
         self.wait()
+        return out
+
+    def reset(self, **kw):
+        self._each(lambda i, e: e.reset(**{key: self._rows(v, i) for key, v in kw.items()}))
         return self._obs, {}
 
     def step_async(self, i, actions):
@@ -789,45 +763,35 @@ class SubBatchedVecEnv:
         self.wait()
         return self._step_out
 
+    def _cat(self, parts, keys):
+        return SimpleNamespace(**{key: torch.cat([getattr(p, key) for p in parts]) for key in keys})
+
     def get_state(self):
-        self.wait()
-        parts = [e.get_state() for e in self.envs]
-        return SimpleNamespace(**{key: torch.cat([getattr(p, key) for p in parts]) for key in
-                                  ("grids", "pos", "counters", "stats", "last_loss", "ep_return", "iteration", "changes", "n_step", "ep_len")})
+        return self._cat(self._each(lambda i, e: e.get_state()),
+                         ("grids", "pos", "counters", "stats", "last_loss", "ep_return", "iteration", "changes", "n_step", "ep_len"))
 
     def reduce_episodes(self, clear=True):
-        self.wait()
-        return torch.stack([e.reduce_episodes(clear=clear) for e in self.envs]).sum(0)
+        return torch.stack(self._each(lambda i, e: e.reduce_episodes(clear=clear))).sum(0)
 
     def last_episode(self):
-        self.wait()
-        parts = [e.last_episode() for e in self.envs]
-        return SimpleNamespace(**{key: torch.cat([getattr(p, key) for p in parts]) for key in ("ep_return", "ep_len", "final_stats", "n_episodes")})
+        return self._cat(self._each(lambda i, e: e.last_episode()), ("ep_return", "ep_len", "final_stats", "n_episodes"))
 
     def sample_actions(self, seed=0):
         """one device-side draw per sub-batch (sub-batch i uses seed + i: its engines keep their own draw counters)"""
-        self.wait()
-        return torch.cat([e.sample_actions(seed + i) for i, e in enumerate(self.envs)])
+        return torch.cat(self._each(lambda i, e: e.sample_actions(seed + i)))
 
     def observe(self):
-        for i, e in enumerate(self.envs):
-            self._fork(i)
-            with torch.cuda.stream(self.streams[i]):
-                e.observe()
-        self.wait()
+        self._each(lambda i, e: e.observe())
         return self._obs
 
     def state_dict(self):
         """a list of the sub-batches' checkpoints (VecPcgrlEnv.state_dict); loads into an env with the same split"""
-        self.wait()
-        return {"sub_batches": [e.state_dict() for e in self.envs]}
+        return {"sub_batches": self._each(lambda i, e: e.state_dict())}
 
     def load_state_dict(self, sd, mask=None):
         if len(sd.get("sub_batches", ())) != self.k:
             raise ValueError(f"state_dict of {len(sd.get('sub_batches', ()))} sub-batches, this env has {self.k}")
-        self.wait()
-        for i, (e, part) in enumerate(zip(self.envs, sd["sub_batches"])):
-            e.load_state_dict(part, mask=self._rows(mask, i))
+        self._each(lambda i, e: e.load_state_dict(sd["sub_batches"][i], mask=self._rows(mask, i)))
 
     def check_errors(self):
         for e in self.envs:
@@ -835,26 +799,25 @@ class SubBatchedVecEnv:
 
     # -- the rest of VecPcgrlEnv's surface, fanned out over the sub-batches ---------------------------------------------
     def _rows(self, v, i):
-        n = self.n_sub
-        return None if v is None else torch.as_tensor(v)[i * n:(i + 1) * n]
+        """sub-batch i's rows of a per-env value; None, scalars (0-dim tensors too) and (lo, hi) target tuples are the same
+        for every sub-batch"""
+        if v is None or isinstance(v, tuple) or np.ndim(v) == 0:
+            return v
+        return (v if hasattr(v, "shape") else torch.as_tensor(v))[i * self.n_sub:(i + 1) * self.n_sub]
 
     def seed(self, seeds):
         s = np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,))
-        for i, e in enumerate(self.envs):
-            e.seed(s[i * self.n_sub:(i + 1) * self.n_sub])
+        self._each(lambda i, e: e.seed(self._rows(s, i)))
 
     def set_static(self, static_prob=None, n_static_walls=None, eval_mode=None):
-        for e in self.envs:
+        for e in self.envs:  # (engine parameters on the host, read by the next reset)
             e.set_static(static_prob, n_static_walls, eval_mode)
 
     def get_static(self):
-        self.wait()
-        return torch.cat([e.get_static() for e in self.envs])
+        return torch.cat(self._each(lambda i, e: e.get_static()))
 
     def queue_targets(self, trgs, mask=None):
-        for i, e in enumerate(self.envs):
-            e.queue_targets({k: (v if isinstance(v, tuple) or not hasattr(v, "__len__") else self._rows(v, i)) for k, v in trgs.items()},
-                            mask=self._rows(mask, i))
+        self._each(lambda i, e: e.queue_targets({k: self._rows(v, i) for k, v in trgs.items()}, mask=self._rows(mask, i)))
 
     def set_target_resampling(self, enable=True, seed=0):
         raise NotImplementedError("target resampling draws from (seed, env index): per sub-batch the env indices restart at 0 -- use one "
@@ -866,12 +829,10 @@ class SubBatchedVecEnv:
         return None if self.envs[0].ctrl_obs is None else torch.cat([e.ctrl_obs for e in self.envs])
 
     def get_rng_state(self):
-        self.wait()
-        return torch.cat([e.get_rng_state() for e in self.envs])
+        return torch.cat(self._each(lambda i, e: e.get_rng_state()))
 
     def set_rng_state(self, rng, mask=None):
-        for i, e in enumerate(self.envs):
-            e.set_rng_state(self._rows(rng, i), mask=self._rows(mask, i))
+        self._each(lambda i, e: e.set_rng_state(self._rows(rng, i), mask=self._rows(mask, i)))
 
     def solver_pool_slots(self):
         """(slots, full size, failed) summed over the sub-batches' engines (each keeps a pool of its own)"""

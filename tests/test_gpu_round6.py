@@ -357,6 +357,54 @@ def test_sub_batched_env_forwards_the_rest_of_the_surface():
     sb.check_errors(); one.check_errors()
 
 
+def test_sub_batched_queue_targets_takes_a_0dim_tensor_as_a_scalar():
+    from control_pcgrl_amd import SubBatchedVecEnv
+    n, kw = 64, dict(controls=["regions", "path-length"])
+    sb = SubBatchedVecEnv("binary", "narrow", (16, 16), n, 2, seeds=np.arange(n), **kw)
+    one = _vec("binary", "narrow", (16, 16), n, seeds=np.arange(n), **kw)
+    for e in (sb, one):
+        e.queue_targets({"regions": torch.tensor(3.0, device="cuda"), "path-length": (10, 20)})
+        e.reset()
+    assert torch.equal(sb.ctrl_obs, one.ctrl_obs)
+    sb.check_errors(); one.check_errors()
+
+
+def test_sub_batched_setters_are_ordered_after_step_async_without_wait():
+    """queue_targets / set_rng_state issued while sub-batch launches are in flight act after them: the same state as one
+    VecPcgrlEnv that makes the same calls in order (auto-resets inside the steps draw from the RNG streams and targets)"""
+    from control_pcgrl_amd import SubBatchedVecEnv
+    n, k, kw = 1024, 2, dict(controls=["regions", "path-length"], change_percentage=0.02)
+    sb = SubBatchedVecEnv("binary", "narrow", (32, 32), n, k, seeds=np.arange(n), **kw)
+    one = _vec("binary", "narrow", (32, 32), n, seeds=np.arange(n), **kw)
+    rng = _vec("binary", "narrow", (32, 32), n, seeds=5000 + np.arange(n), **kw).get_rng_state()
+    for e in (sb, one):
+        e.reset()
+    g = torch.Generator().manual_seed(7)
+    for t in range(40):
+        acts = torch.randint(0, 2, (n,), generator=g, dtype=torch.int32).cuda()
+        trgs = {"regions": torch.full((n,), float(1 + t % 4), dtype=torch.float64, device="cuda"), "path-length": float(t % 30)}
+        for i in range(k):
+            sb.step_async(i, acts[i * n // k:(i + 1) * n // k])
+        sb.queue_targets(trgs)
+        sb.set_rng_state(rng)
+        one.step(acts)
+        one.queue_targets(trgs)
+        one.set_rng_state(rng)
+    sb.wait()
+    a, b = sb.get_state(), one.get_state()
+    assert torch.equal(a.grids, b.grids) and torch.equal(a.counters, b.counters) and torch.equal(a.stats, b.stats)
+    assert torch.equal(sb.get_rng_state(), one.get_rng_state())
+    assert torch.equal(sb.ctrl_obs, one.ctrl_obs)
+    assert int(one.last_episode().n_episodes.sum()) > 0, "no auto-reset: the steps did not read the RNG streams"
+    sb.check_errors(); one.check_errors()
+
+
+def test_step_ready_before_set_solver_budget_raises():
+    env = _vec("sokoban", "wide", (16, 16), 8, seeds=np.arange(8))
+    with pytest.raises(ValueError, match="set_solver_budget"):
+        env.step_ready(torch.zeros(8, dtype=torch.int32, device="cuda"))
+
+
 def test_step_ready_captured_in_a_hip_graph_equals_eager_launches():
     """pcgrl_step_ready takes no host-side decision per launch: a captured chain of T launches (each with its own status row)
     replays to exactly what T eager launches of a twin engine produce -- statuses, stats, rewards"""
