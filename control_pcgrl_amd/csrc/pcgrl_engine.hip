@@ -1369,6 +1369,29 @@ int pcgrl_import_state(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_b
   if (hdr.n_envs != h->p.n_envs || hdr.n_arrays != (int32_t)h->state_arrays.size() || hdr.total_bytes != (uint64_t)pcgrl_state_bytes(h) ||
       hdr.fingerprint != state_fingerprint(h))
     return fail(PCGRL_EINVAL, "pcgrl_import_state: the image was exported by an engine with another config, batch size or library version");
+  // asynchronous stepping and the synchronous kernels each lack the other's per-env states: the resumable kernels carry no
+  // code for statistics left stale by pcgrl_update, the synchronous ones none for a parked search (ENV_PENDING_STEP /
+  // ENV_PENDING_STATS and pend_action would be ignored, not played).  Refused as pcgrl_set_solver_budget refuses them.
+  if (h->sk_budget > 0 && maybe_stale != 0)
+    return fail(PCGRL_EINVAL, "pcgrl_import_state: the image may carry statistics left stale by pcgrl_update, which the asynchronous "
+                              "kernels have no code for (a solver budget is set): call pcgrl_refresh_stats before exporting");
+  if (h->sk_budget == 0 && h->p.soko) {
+    const int32_t n = h->p.n_envs;
+    size_t st_off = STATE_HDR_BYTES;
+    for (auto &a : h->state_arrays) {
+      if (a.first == (void *)h->p.st) break;
+      st_off += state_section(a.second * (size_t)n);
+    }
+    std::vector<EnvState> st(n);
+    std::vector<uint8_t> m(d_mask != nullptr ? n : 0);
+    HIPCHK(hipMemcpyAsync(st.data(), d_buf + st_off, (size_t)n * sizeof(EnvState), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (d_mask != nullptr) HIPCHK(hipMemcpyAsync(m.data(), d_mask, (size_t)n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    for (int32_t i = 0; i < n; i++)
+      if ((d_mask == nullptr || m[i] != 0) && (st[i].flags & (ENV_PENDING_STEP | ENV_PENDING_STATS)) != 0)
+        return fail(PCGRL_EINVAL, "pcgrl_import_state: env " + std::to_string(i) + " of the image is busy (a parked search of an engine "
+                                  "with a solver budget), which only pcgrl_step_ready can finish: set a solver budget first");
+  }
   if (d_mask == nullptr && h->p.cfg.static_tiles) {
     // the exporter's run-time static-tile parameters (a curriculum's set_static_prob, evaluation mode) come with the image;
     // a masked import leaves the engine-wide parameters as they are
@@ -1478,6 +1501,7 @@ int pcgrl_step_ready(pcgrl_handle h, const int32_t *d_actions, int32_t auto_rese
   ON_DEVICE(h->device);
   Params p = h->p;
   p.no_fast = h->maybe_stale ? 1 : 0;
+  soko_pool_lazy(h, p, (hipStream_t)stream);  // (levels of more than SK_MAXC pairs run the synchronous solver on the pool)
   p.spread = 1;  // one env per workgroup: every search has a wavefront of its own
   p.sk_helpers = 0;
   p.sk_budget = h->sk_budget;

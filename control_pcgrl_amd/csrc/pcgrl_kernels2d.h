@@ -642,7 +642,7 @@ __device__ __attribute__((always_inline)) inline void touch_kernarg(const Params
                "s"(kw[208 < sizeof(Params) / 4 ? 208 : 0]));
 }
 
-template <int LPE, typename M, bool HUGE>
+template <int LPE, typename M, bool HUGE, bool ONLY_HUGE = false>
 __device__ void sokoban_solve(const Grp<LPE> &g, const Params &p, int env, bool need, M solid, M player, M crate, M target,
                               int &dist_win, int &sol_len);
 // asynchronous stepping: the solver to a per-launch budget, on the env's own workspace (pcgrl_sokoban.h "resumable solver")
@@ -655,6 +655,7 @@ __device__ inline void sokoban_helper(const Params &p, int k, uint32_t *lds_heap
 // ... each with an expander wave behind it (A* stage k = heap wave k + expander wave k, see sk_stage_heap): kernels
 // launched with sk_helpers = 3 carry 2 * 3 helper wavefronts, the heap waves first
 __device__ inline void sokoban_expander(const Params &p, int k);
+constexpr int SK_MAXC = 128;  // sokoban: the most crate / target pairs one stage workspace holds (pcgrl_sokoban.h)
 constexpr int SK_HELPER_LDS = 32 * 1024;  // dynamic LDS per helper wave (the top of its A* heap), behind the kernel's own
 __device__ inline void sokoban_helpers_init();
 __device__ inline void sokoban_helpers_release();
@@ -790,7 +791,17 @@ __device__ inline void compute_stats(const Grp<LPE> &g, const Params &p, int env
     if (__ballot(need) != 0) {
       if constexpr (SKA) {
         const M lvl[3] = {b[0] & cm, b[1] & cm, b[2] & cm};
-        const bool u = sokoban_solve_async<LPE, M>(g, p, env, need, solid, player, crate, target, lvl, dist_win, sol_len);
+        bool u = false;
+        if constexpr (SK_HUGE) {
+          // more pairs than a stage workspace holds (SK_MAXC; maps of >= 258 cells only): the synchronous search, to the end
+          // within this launch -- such a level is not resumable, but its statistics are exact.  (Not in the compile-time
+          // 16x16 kernels: 256 cells hold at most 127 pairs.)
+          const bool huge = need && n_crate > SK_MAXC, part = need && !huge;
+          if (__ballot(huge) != 0) sokoban_solve<LPE, M, true, true>(g, p, env, huge, solid, player, crate, target, dist_win, sol_len);
+          if (__ballot(part) != 0) u = sokoban_solve_async<LPE, M>(g, p, env, part, solid, player, crate, target, lvl, dist_win, sol_len);
+        } else {
+          u = sokoban_solve_async<LPE, M>(g, p, env, need, solid, player, crate, target, lvl, dist_win, sol_len);
+        }
         if (unfinished != nullptr) *unfinished = u;
       } else {
         sokoban_solve<LPE, M, SK_HUGE>(g, p, env, need, solid, player, crate, target, dist_win, sol_len);
@@ -2456,7 +2467,18 @@ __global__ __launch_bounds__(64) void reset_kernel(Params p) {
   }
   int32_t st[NS];
   bool unfin = false;
-  compute_stats<PROB, LPE, M, true, SKA>(g, p, e, active, b, colmask, st, -1, SKA ? &unfin : nullptr);
+  // SKA, pcgrl_refresh_stats: an env with a parked step is left alone -- nothing of the step is committed and pcgrl_update is
+  // refused under a budget, so its statistics are those of its map already; restarting its search here could park it again
+  // as ENV_PENDING_STATS on top of ENV_PENDING_STEP, and the launch finishing those would report the env idle too early
+  const bool keep = SKA && p.refresh_only && active && (S->flags & ENV_PENDING_STEP) != 0;
+  compute_stats<PROB, LPE, M, true, SKA>(g, p, e, active && !keep, b, colmask, st, -1, SKA ? &unfin : nullptr);
+  if (keep) {  // (one env per wavefront: uniform over its lanes)
+    if (g.row == 0 && p.stats_out) {
+#pragma unroll
+      for (int k = 0; k < NS; k++) p.stats_out[(size_t)e * NS + k] = S->stats[k];
+    }
+    return;
+  }
   store_planes<NW, M>(p, e, g.row, rowok, b);
   if constexpr (PROB == PCGRL_PROB_BINARY) {  // PREFLOOD plane: stale after a reset (map and position changed)
     if (rowok && !p.refresh_only) ((M *)p.planes)[((size_t)e * ROW_WORDS + PRE_PLANE) * H + g.row] = M(0);

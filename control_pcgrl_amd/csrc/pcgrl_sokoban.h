@@ -64,8 +64,8 @@ namespace pcgrl {
   } while (0)
 #endif
 
-constexpr int SK_MAXC = 128;     // crates (= targets) of a level the wave-cooperative solver keeps in two registers per lane, and
-                                 // the crate-list area of a node in a stage workspace (a 16x16 map holds at most 127 pairs + player)
+// SK_MAXC (pcgrl_kernels2d.h, 128): crates (= targets) of a level the wave-cooperative solver keeps in two registers per
+// lane, and the crate-list area of a node in a stage workspace (a 16x16 map holds at most 127 pairs + player)
 constexpr int SK_NH_HUGE = 8;    // levels with more pairs (maps of >= 258 cells can have them): 8 registers per lane, up to
 constexpr int SK_MAXC_HUGE = 64 * SK_NH_HUGE;  // 512 pairs; their node crate lists spread over the crate areas of the slot's
                                  // four stage workspaces (sk_crate_ptr), the stages run one after the other on the simulate wave
@@ -1338,8 +1338,9 @@ __device__ __attribute__((always_inline)) inline void sk_build_level(const Grp<L
 // solver are served one after the other by the WHOLE wave, so a wavefront holds at most one workspace slot at a time
 // and never waits for a slot while holding one.
 // HUGE: the kernel also carries the search for levels with more than SK_MAXC pairs (every kernel except the compile-time
-// 16x16 ones, whose maps hold at most 127 pairs)
-template <int LPE, typename M, bool HUGE>
+// 16x16 ones, whose maps hold at most 127 pairs).  ONLY_HUGE: nothing else -- the resumable kernels' path for the levels
+// their stage workspace cannot hold (compute_stats; without the other cascades the kernel keeps its registers)
+template <int LPE, typename M, bool HUGE, bool ONLY_HUGE>
 __device__ __attribute__((always_inline)) inline void sokoban_solve(const Grp<LPE> &g, const Params &p, int env, bool need, M solid, M player,
                                                         M crate, M target, int &dist_win, int &sol_len) {
   (void)env;
@@ -1396,6 +1397,8 @@ __device__ __attribute__((always_inline)) inline void sokoban_solve(const Grp<LP
         // helper waves, if any, get no job and keep waiting)
         if constexpr (HUGE) won = sk_cascade<SK_NH_HUGE>(c, pool, slot, p.cfg.solver_power, px, py, h, depth);
         else won = false;
+      } else if constexpr (ONLY_HUGE) {
+        won = false;  // (not reached: the caller hands over levels of more than SK_MAXC pairs only)
       } else if (p.sk_helpers != 0) {
         if (ncr > 64) won = sk_cascade_helped<2>(c, pool, slot, p.cfg.solver_power, px, py, h, depth);
         else won = sk_cascade_helped<1>(c, pool, slot, p.cfg.solver_power, px, py, h, depth);
@@ -1553,8 +1556,9 @@ __device__ __attribute__((always_inline)) inline bool sokoban_solve_async(const 
     sk_build_level<LPE, M, SK_MAXC>(g, gi, H, W, solid, player, crate, target, px, py, ncr, ntg);
     bool finished = true;
     if (ncr > SK_MAXC || ntg > SK_MAXC || W + 2 > SK_MAXDIM || H + 2 > SK_MAXDIM) {
-      // beyond what one stage workspace holds (more than 128 pairs: maps of >= 258 cells only): reported by pcgrl_poll_error,
-      // the level keeps the solver-less statistics
+      // beyond what one stage workspace holds (more than 128 pairs: maps of >= 258 cells only).  compute_stats hands such
+      // levels to the synchronous solver (sokoban_solve with HUGE) instead; reaching this is a limit, reported by
+      // pcgrl_poll_error, and the level keeps the solver-less statistics
       if (g.lane == 0) atomicOr(p.err, 2);
     } else {
       c.ncr = ncr;

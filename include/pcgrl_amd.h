@@ -213,7 +213,12 @@ int pcgrl_ctrl_observe(pcgrl_handle h, float *d_ctrl_obs, void *stream);
  *                        stale": pcgrl_get_state keeps returning the old statistics (the reference's _rep_stats), and the
  *                        next pcgrl_step that changes its map recomputes them from scratch (pcgrl_env.py:314-323)
  *   pcgrl_refresh_stats  Problem.get_stats() of the current maps -> engine state (and d_stats int32 [N][n_stats] if
- *                        non-NULL); also re-bases the loss so that later pcgrl_step rewards are consistent */
+ *                        non-NULL); also re-bases the loss so that later pcgrl_step rewards are consistent.  With a solver
+ *                        budget (asynchronous stepping, below): an env with a parked step is left as it is -- its row of
+ *                        d_stats holds the statistics of its current map (the step's own map is not committed yet) and it
+ *                        stays busy with that step; an env whose level's search does not end within the budget becomes
+ *                        busy (PCGRL_ENV_BUSY semantics: its statistics arrive with a later pcgrl_step_ready launch, which
+ *                        then reports 0) and its row is not written */
 int pcgrl_update(pcgrl_handle h, const int32_t *d_actions, uint8_t *d_obs, void *stream);
 int pcgrl_refresh_stats(pcgrl_handle h, int32_t *d_stats, void *stream);
 
@@ -299,6 +304,13 @@ int pcgrl_poll_error(pcgrl_handle h);
  *                       a masked import leaves the engine-wide parameters alone.  pcgrl_export_state copies the header
  *                       from pinned memory owned by the engine: capturable, replays carry the current parameters.  Reading the header waits for `stream` once (the only
  *                       synchronising call among the state entry points; not to be captured in a HIP graph).
+ *                       Across solver modes (pcgrl_set_solver_budget), refused with PCGRL_EINVAL in the same way, as
+ *                       pcgrl_set_solver_budget refuses these states: into a sokoban engine WITHOUT a budget, an image in
+ *                       which an env the import covers is busy (a parked step or a reset waiting for its statistics; the
+ *                       flags are read from the image on the host: one more wait for `stream`); into an engine WITH a
+ *                       budget, an image exported with maybe_stale = 1.  Any other combination continues exactly: a
+ *                       synchronous image in a budgeted engine, a budgeted image without busy envs (or a masked import of
+ *                       its idle envs) in a synchronous engine, an older image back in the same engine.
  * The buffer is an opaque image for this library version and config; pcgrl_get_state / pcgrl_set_state remain the
  * portable (maps, positions, counters) form. */
 int64_t pcgrl_state_bytes(pcgrl_handle h);
@@ -328,7 +340,10 @@ int pcgrl_import_state(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_b
  *   pcgrl_env_busy(h, d_busy, stream)    uint8 [N]: 1 = the env is busy now (what the last launch's PCGRL_ENV_BUSY said, or what
  *       a pcgrl_reset left behind)
  * A search is resumed only for exactly the level it was started on (the park record carries the map); anything else -- a reset,
- * an imported checkpoint, a step abandoned by pcgrl_reset -- restarts it: results never depend on parked state. */
+ * an imported checkpoint, a step abandoned by pcgrl_reset -- restarts it: results never depend on parked state.
+ * Levels with more than 128 crate / target pairs (maps of >= 258 cells only) do not fit an env's stage workspace: their search
+ * runs synchronously on the solver pool (pcgrl_reserve_solver_pool) to the end within the launch -- exact, like pcgrl_step, but
+ * NOT resumable: such a launch lasts as long as that search. */
 enum { PCGRL_ENV_EMITTED = 1, PCGRL_ENV_BUSY = 2 };
 int pcgrl_set_solver_budget(pcgrl_handle h, int32_t budget);
 int32_t pcgrl_get_solver_budget(pcgrl_handle h);
