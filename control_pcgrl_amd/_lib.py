@@ -11,8 +11,9 @@ LIB_PATH = os.path.join(CSRC, "libpcgrl_amd.so")
 UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pcgrl_k_zelda32.hip", "pcgrl_k_zelda64.hip",
          "pcgrl_k_sokoban32_8.hip", "pcgrl_k_sokoban32_16.hip", "pcgrl_k_sokoban32_32.hip",
          "pcgrl_k_sokoban32_64.hip", "pcgrl_k_sokoban64_32.hip", "pcgrl_k_sokoban64_64.hip", "pcgrl_k_3d.hip",
-         "codes/pcgrl_codes.hip"]
-HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h"]
+         "codes/pcgrl_codes.hip", "reps3d/pcgrl_k_3d_turtle.hip", "reps3d/pcgrl_k_3d_wide.hip"]
+HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
+           "reps3d/pcgrl_reps3d.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")

@@ -21,6 +21,7 @@
 #include "pcgrl_sokoban.h"    // sokoban_alloc
 #include "pcgrl_kernels3d.h"  // M3_* limits
 #include "codes/pcgrl_codes.h"
+#include "reps3d/pcgrl_reps3d.h"  // the 3-D maze under turtle / wide
 #include "../../include/pcgrl_amd_codes.h"
 
 using namespace pcgrl;
@@ -171,11 +172,22 @@ static int validate(const pcgrl_config &c, int &lpe, int64_t &obs_bytes, int &ob
     if (c.ndim != 3) return fail(PCGRL_EINVAL, "minecraft_3D_maze needs ndim == 3");
     if (c.static_tiles || c.act_window[0] != 0)
       return fail(PCGRL_EUNSUPPORTED, "static tiles / act_window are only on the accelerated path for 2-D problems");
-    if (c.representation != PCGRL_REP_NARROW)
-      return fail(PCGRL_EUNSUPPORTED, "minecraft_3D_maze: only the narrow representation is on the accelerated path");
     const int Z = c.dims[0], Y = c.dims[1], X = c.dims[2];
     if (!m3_supported(Z, Y, X))
       return fail(PCGRL_EUNSUPPORTED, "minecraft_3D_maze: need 1 <= Z, Y, X <= 16 (the reference's stock map is 15 x 15 x 15)");
+    if (c.representation == PCGRL_REP_WIDE) {  // wide_rep.py: the observation is the whole map, not a crop
+      if (c.obs_window[0] != Z || c.obs_window[1] != Y || c.obs_window[2] != X)
+        return fail(PCGRL_EINVAL, "wide representation needs obs_window == map_shape");
+      lpe = 64;
+      obs_chunks = 0;
+      obs_bytes = (int64_t)Z * Y * X * 3;
+      shape[0] = Z;
+      shape[1] = Y;
+      shape[2] = X;
+      shape[3] = 3;  // AIR, DIRT, path overlay
+      ndim = 4;
+      return PCGRL_OK;
+    }
     const int64_t cells = (int64_t)c.obs_window[0] * c.obs_window[1] * c.obs_window[2];
     if (cells < 1 || cells % 4) return fail(PCGRL_EUNSUPPORTED, "3-D obs_window volume must be a positive multiple of 4");
     lpe = 64;
@@ -270,7 +282,10 @@ static bool obs_nt_for(const pcgrl_engine *e, int64_t bytes_per_launch) {
 static hipError_t launch(KernelId id, int lpe, const Params &p, size_t lds, hipStream_t s, int cpl = 0) {
   const bool wide64 = p.cfg.dims[1] > 32;  // 64-bit row masks (W <= 64); validate() guarantees lpe >= 32 there
   switch (p.cfg.problem) {
-    case PCGRL_PROB_MC3DMAZE: return launch_3d(id, p, cpl, s);
+    case PCGRL_PROB_MC3DMAZE:
+      if (p.cfg.representation == PCGRL_REP_TURTLE) return launch_3d_turtle(id, p, cpl, s);
+      if (p.cfg.representation == PCGRL_REP_WIDE) return launch_3d_wide(id, p, cpl, s);
+      return launch_3d(id, p, cpl, s);
     case PCGRL_PROB_BINARY: return wide64 ? launch_binary64(id, lpe, p, lds, s) : launch_binary32(id, lpe, p, lds, s);
     case PCGRL_PROB_ZELDA: return wide64 ? launch_zelda64(id, lpe, p, lds, s) : launch_zelda32(id, lpe, p, lds, s);
     default: return wide64 ? launch_sokoban64(id, lpe, p, lds, s) : launch_sokoban32(id, lpe, p, lds, s);
@@ -1596,7 +1611,14 @@ static void codes_layout(const pcgrl_engine *h, int32_t shape[4], int *ndim, int
   const pcgrl_config &c = h->p.cfg;
   const int nt = h->p.n_tiles;
   shape[0] = shape[1] = shape[2] = shape[3] = 0;
-  if (c.problem == PCGRL_PROB_MC3DMAZE) {
+  if (c.problem == PCGRL_PROB_MC3DMAZE && c.representation == PCGRL_REP_WIDE) {
+    shape[0] = c.dims[0];  // obs["map"] itself: 0 AIR, 1 DIRT, 2 path overlay
+    shape[1] = c.dims[1];
+    shape[2] = c.dims[2];
+    shape[3] = 1;
+    *ndim = 4;
+    *C = *CS = 3;
+  } else if (c.problem == PCGRL_PROB_MC3DMAZE) {
     shape[0] = c.obs_window[0];
     shape[1] = c.obs_window[1];
     shape[2] = c.obs_window[2];

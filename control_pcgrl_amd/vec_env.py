@@ -90,7 +90,8 @@ _CONFIG_ARGS = tuple(inspect.signature(build_config).parameters)[3:]  # (the key
 # Observation forms.  "onehot" (default): the reference's image, uint8 [N, OH, OW, C] (wrappers.py:407-437 Cropped ->
 # :232-257 OneHotEncoding -> :140-150 ToImage).  "codes": the same stack without OneHotEncoding, one byte per cell and plane
 # (include/pcgrl_amd_codes.h): narrow / turtle [N, OH, OW, 1 + static_tiles] (0 = outside the map, 1 + tile; the static mask),
-# wide [N, H, W, 1] (tile), 3-D [N, o0, o1, o2, 1] (index of the one-hot channel).  codes_to_onehot() restores the image.
+# wide [N, H, W, 1] (tile), 3-D [N, o0, o1, o2, 1] (index of the one-hot channel; 3-D wide [N, d0, d1, d2, 1]: 0 AIR, 1 DIRT,
+# 2 path).  codes_to_onehot() restores the image.
 OBS_FORMATS = ("onehot", "codes")
 _ROLLOUT_SCRATCH_BYTES = 256 << 20  # one-hot scratch of a codes rollout that keeps every step: chunks of steps up to this size
 # codes rollout(want_obs="all"), 2-D: K x (step + encoder) where the one-hot image has more bytes per cell than this, else the
@@ -108,6 +109,8 @@ def obs_shape_for(cfg, spec, obs_window, obs_format="onehot"):
     """per-env observation shape of a build_config() result in either form (what pcgrl_obs_shape / pcgrl_codes_shape return)"""
     _check_obs_format(obs_format)
     nt, static = spec.n_tiles, 1 if cfg.static_tiles else 0
+    if cfg.ndim == 3 and cfg.representation == REPRESENTATIONS["wide"]:  # the whole map: AIR, DIRT, path overlay
+        return tuple(cfg.dims[i] for i in range(3)) + ((3,) if obs_format == "onehot" else (1,))
     if cfg.ndim == 3:
         return tuple(obs_window) + ((4,) if obs_format == "onehot" else (1,))
     if cfg.representation == REPRESENTATIONS["wide"]:
@@ -118,9 +121,21 @@ def obs_shape_for(cfg, spec, obs_window, obs_format="onehot"):
 def _onehot_channels(problem, representation, map_shape):
     """one-hot channels plane 0 of the codes expands to"""
     if len(tuple(map_shape)) == 3:
-        return 4
+        return 3 if representation == "wide" else 4  # wide: obs["map"] itself (AIR, DIRT, path), nothing out of bounds
     nt = problem_spec(problem, map_shape).n_tiles
     return nt if representation == "wide" else nt + 1
+
+
+def flatten_wide_action(action, map_shape, n_tiles):
+    """The engine's int32 action of the wide representation from the reference's MultiDiscrete one ([..., ndim + 1] =
+    cell index per axis + tile; wide_rep.py: `action[:-1]` indexes the map as it is): the C-order flat index over
+    (*map_shape, n_tiles), i.e. np.ravel_multi_index(action, (*map_shape, n_tiles)).  3-D maze: (d0, d1, d2, tile).
+    (The 2-D problems' flat wide action is the reference ActionMap's, which this also equals.)"""
+    a = np.asarray(action, dtype=np.int64)
+    dims = tuple(int(d) for d in map_shape) + (int(n_tiles),)
+    if a.shape[-1] != len(dims):
+        raise ValueError(f"wide action needs {len(dims)} entries per env, got shape {a.shape}")
+    return np.ravel_multi_index(tuple(np.moveaxis(a, -1, 0)), dims).astype(np.int32)
 
 
 def codes_high(env):
