@@ -22,7 +22,9 @@
 #include "pcgrl_kernels3d.h"  // M3_* limits
 #include "codes/pcgrl_codes.h"
 #include "reps3d/pcgrl_reps3d.h"  // the 3-D maze under turtle / wide
+#include "async3d/pcgrl_async3d.h"  // the 3-D maze (narrow) under a solver budget
 #include "../../include/pcgrl_amd_codes.h"
+#include "../../include/pcgrl_amd_async3d.h"
 
 using namespace pcgrl;
 
@@ -52,6 +54,7 @@ struct pcgrl_engine {
   int32_t seen_last = 0, spread_left = 0;
   bool soko_lazy = true;         // grow the solver pool by itself the first time the solver has been seen running
   int sk_budget = 0;             // sokoban, asynchronous stepping: solver iteration units per env and launch (0 = synchronous)
+  void *a3_park = nullptr;       // 3-D maze (narrow), asynchronous stepping: one park record per env (async3d/pcgrl_async3d.h)
   void *sk_ws = nullptr, *sk_park = nullptr;  // ... and its per-env stage workspaces / park records (also in the device SokoPool)
   bool soko_grow_failed = false; // the last growth attempt failed (message in soko_grow_msg): not retried by itself
   std::string soko_grow_msg;
@@ -285,6 +288,8 @@ static hipError_t launch(KernelId id, int lpe, const Params &p, size_t lds, hipS
     case PCGRL_PROB_MC3DMAZE:
       if (p.cfg.representation == PCGRL_REP_TURTLE) return launch_3d_turtle(id, p, cpl, s);
       if (p.cfg.representation == PCGRL_REP_WIDE) return launch_3d_wide(id, p, cpl, s);
+      // asynchronous stepping: the resumable kernels, the park records in Params::soko (with_budget)
+      if (p.sk_budget > 0 && (id == K_STEP || id == K_RESET)) return launch_3d_async(id, p, cpl, s);
       return launch_3d(id, p, cpl, s);
     case PCGRL_PROB_BINARY: return wide64 ? launch_binary64(id, lpe, p, lds, s) : launch_binary32(id, lpe, p, lds, s);
     case PCGRL_PROB_ZELDA: return wide64 ? launch_zelda64(id, lpe, p, lds, s) : launch_zelda32(id, lpe, p, lds, s);
@@ -831,6 +836,16 @@ int pcgrl_seed(pcgrl_handle h, const uint64_t *seeds) {
   return PCGRL_OK;
 }
 
+// the per-launch parameters of asynchronous stepping: the budget and, on a 3-D maze engine, the park records (Params::soko is
+// null there otherwise and stays null in h->p: the engine reads h->p.soko as "this engine has the sokoban solver")
+static void with_budget(const pcgrl_engine *h, Params &p) {
+  p.sk_budget = h->sk_budget;
+  if (h->sk_budget > 0 && h->a3_park) p.soko = h->a3_park;
+}
+static bool async_capable(const pcgrl_engine *h) {
+  return h->p.soko != nullptr || (h->p.cfg.problem == PCGRL_PROB_MC3DMAZE && h->p.cfg.representation == PCGRL_REP_NARROW);
+}
+
 int pcgrl_reset(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_init_grids, const int32_t *d_init_pos, void *stream) {
   if (!h) return fail(PCGRL_EINVAL, "pcgrl_reset: null handle");
   ON_DEVICE(h->device);
@@ -839,7 +854,7 @@ int pcgrl_reset(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_init_gri
   p.mask = d_mask;
   p.init_grids = d_init_grids;
   p.init_pos = d_init_pos;
-  p.sk_budget = h->sk_budget;  // (asynchronous stepping: a playable level's search may stay parked, the env busy)
+  with_budget(h, p);  // (asynchronous stepping: a search may stay parked, the env busy)
   HIPCHK(launch(K_RESET, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
   if (d_mask == nullptr) h->maybe_stale = false;
   return PCGRL_OK;
@@ -1058,7 +1073,7 @@ int pcgrl_refresh_stats(pcgrl_handle h, int32_t *d_stats, void *stream) {
   Params p = h->p;
   p.refresh_only = 1;
   p.stats_out = d_stats;
-  p.sk_budget = h->sk_budget;
+  with_budget(h, p);
   HIPCHK(launch(K_RESET, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
   h->maybe_stale = false;
   return PCGRL_OK;
@@ -1287,7 +1302,7 @@ int pcgrl_set_state(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_grid
   p.in_counters = d_counters;
   p.in_ep_return = d_ep_return;
   p.set_state = 1;
-  p.sk_budget = h->sk_budget;
+  with_budget(h, p);
   HIPCHK(launch(K_RESET, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
   if (d_mask == nullptr) h->maybe_stale = false;
   return PCGRL_OK;
@@ -1390,7 +1405,7 @@ int pcgrl_import_state(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_b
   if (h->sk_budget > 0 && maybe_stale != 0)
     return fail(PCGRL_EINVAL, "pcgrl_import_state: the image may carry statistics left stale by pcgrl_update, which the asynchronous "
                               "kernels have no code for (a solver budget is set): call pcgrl_refresh_stats before exporting");
-  if (h->sk_budget == 0 && h->p.soko) {
+  if (h->sk_budget == 0 && async_capable(h)) {  // (the mode, whatever the problem: every engine that can leave envs busy)
     const int32_t n = h->p.n_envs;
     size_t st_off = STATE_HDR_BYTES;
     for (auto &a : h->state_arrays) {
@@ -1407,6 +1422,9 @@ int pcgrl_import_state(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_b
         return fail(PCGRL_EINVAL, "pcgrl_import_state: env " + std::to_string(i) + " of the image is busy (a parked search of an engine "
                                   "with a solver budget), which only pcgrl_step_ready can finish: set a solver budget first");
   }
+  // 3-D maze: searches parked in THIS engine belong to the states about to be replaced (parked searches are not in the image)
+  if (h->a3_park)
+    HIPCHK(launch_3d_async_unpark(h->a3_park, h->p.cfg.dims[0], h->p.cfg.dims[1], h->p.cfg.dims[2], h->p.n_envs, d_mask, (hipStream_t)stream));
   if (d_mask == nullptr && h->p.cfg.static_tiles) {
     // the exporter's run-time static-tile parameters (a curriculum's set_static_prob, evaluation mode) come with the image;
     // a masked import leaves the engine-wide parameters as they are
@@ -1477,16 +1495,36 @@ int pcgrl_sample_actions(pcgrl_handle h, int32_t *d_actions, uint64_t seed, void
 
 int pcgrl_set_solver_budget(pcgrl_handle h, int32_t budget) {
   if (!h || budget < 0) return fail(PCGRL_EINVAL, "pcgrl_set_solver_budget: bad arguments");
-  if (h->p.cfg.problem != PCGRL_PROB_SOKOBAN || !h->p.soko)
-    return fail(PCGRL_EUNSUPPORTED, "pcgrl_set_solver_budget: only sokoban has a device solver");
+  const bool maze3d = h->p.cfg.problem == PCGRL_PROB_MC3DMAZE;
+  if (maze3d && h->p.cfg.representation != PCGRL_REP_NARROW)
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_set_solver_budget: minecraft_3D_maze steps asynchronously under the narrow representation only "
+                                    "(the turtle and wide kernels are synchronous)");
+  if (!maze3d && (h->p.cfg.problem != PCGRL_PROB_SOKOBAN || !h->p.soko))
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_set_solver_budget: only sokoban (device solver) and minecraft_3D_maze narrow (path searches) "
+                                    "have resumable searches");
   if (h->p.ext || h->p.cfg.n_ctrl > 0)
-    return fail(PCGRL_EUNSUPPORTED, "pcgrl_set_solver_budget: asynchronous stepping is built for sokoban without static tiles, action "
-                                    "patches or control metrics");
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_set_solver_budget: asynchronous stepping is built for sokoban and the 3-D maze without static "
+                                    "tiles, action patches or control metrics");
   if (budget > 0 && h->maybe_stale)
     return fail(PCGRL_EINVAL, "pcgrl_set_solver_budget: statistics left stale by pcgrl_update may exist (the asynchronous kernels carry no "
                               "code for them): call pcgrl_refresh_stats or reset the envs first");
   ON_DEVICE(h->device);
-  if (budget > 0 && h->sk_ws == nullptr) {  // one stage workspace + one park record per env, once
+  if (maze3d && budget > 0 && h->a3_park == nullptr) {  // one park record per env, once (12 320 / 105 760 bytes by size class)
+    HIPCHK(hipDeviceSynchronize());
+    const size_t bytes = a3_park_bytes(h->p.cfg.dims[0], h->p.cfg.dims[1], h->p.cfg.dims[2]) * (size_t)h->p.n_envs;
+    void *pool = nullptr;
+    hipError_t e = hipMalloc(&pool, bytes);
+    if (e == hipSuccess) {
+      h->allocs.push_back(pool);
+      e = hipMemset(pool, 0, bytes);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(PCGRL_EHIP, std::string("pcgrl_set_solver_budget: allocating one park record per env: ") + hipGetErrorString(e));
+    }
+    h->a3_park = pool;
+  }
+  if (!maze3d && budget > 0 && h->sk_ws == nullptr) {  // one stage workspace + one park record per env, once
     HIPCHK(hipDeviceSynchronize());
     const hipError_t e = sokoban_alloc_async(h->p, h->allocs, h->p.n_envs, &h->sk_ws, &h->sk_park);
     if (e != hipSuccess) {
@@ -1509,6 +1547,13 @@ int pcgrl_set_solver_budget(pcgrl_handle h, int32_t budget) {
 
 int32_t pcgrl_get_solver_budget(pcgrl_handle h) { return h ? h->sk_budget : -1; }
 
+// include/pcgrl_amd_async3d.h
+int64_t pcgrl_park_bytes_per_env(pcgrl_handle h) {
+  if (!h) return -1;
+  if (h->p.cfg.problem != PCGRL_PROB_MC3DMAZE || h->p.cfg.representation != PCGRL_REP_NARROW) return 0;
+  return (int64_t)a3_park_bytes(h->p.cfg.dims[0], h->p.cfg.dims[1], h->p.cfg.dims[2]);
+}
+
 int pcgrl_step_ready(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, uint8_t *d_obs, float *d_reward, uint8_t *d_done,
                      int32_t *d_stats, uint8_t *d_status, void *stream) {
   if (!h || !d_actions || !d_status) return fail(PCGRL_EINVAL, "pcgrl_step_ready: bad arguments");
@@ -1519,7 +1564,7 @@ int pcgrl_step_ready(pcgrl_handle h, const int32_t *d_actions, int32_t auto_rese
   soko_pool_lazy(h, p, (hipStream_t)stream);  // (levels of more than SK_MAXC pairs run the synchronous solver on the pool)
   p.spread = 1;  // one env per workgroup: every search has a wavefront of its own
   p.sk_helpers = 0;
-  p.sk_budget = h->sk_budget;
+  with_budget(h, p);
   p.actions = d_actions;
   p.auto_reset = auto_reset;
   p.obs = d_obs;

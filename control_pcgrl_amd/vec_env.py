@@ -434,13 +434,14 @@ class VecPcgrlEnv:
         n = int(self._L.pcgrl_solver_pool_slots(self._h, C.byref(full), C.byref(failed)))
         return n, int(full.value), bool(failed.value)
 
-    # -- asynchronous stepping (sokoban): resumable device solver behind a per-env status byte -----------------------
+    # -- asynchronous stepping (sokoban; the 3-D maze under narrow): resumable searches behind a per-env status byte ----
     EMITTED, BUSY = 1, 2  # include/pcgrl_amd.h PCGRL_ENV_EMITTED / PCGRL_ENV_BUSY
 
     def set_solver_budget(self, budget):
         """budget > 0: the device solver works to `budget` iteration units per env and launch and parks what it could not
         finish; step with step_ready() from here on (step() / rollout() / update() are refused).  0: synchronous again.
-        In the reference a slow _run_game (sokoban_prob.py:99-148) stalls one env, not the fleet (rl/utils.py:412-415)."""
+        In the reference a slow _run_game (sokoban_prob.py:99-148) stalls one env, not the fleet (rl/utils.py:412-415).
+        minecraft_3D_maze under narrow: `budget` = trips of the path search per env and launch (include/pcgrl_amd_async3d.h)."""
         _lib.check(self._L.pcgrl_set_solver_budget(self._h, int(budget)), "pcgrl_set_solver_budget")
         if budget > 0 and self._status is None:
             self._status = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
