@@ -485,6 +485,9 @@ static int base_update(const orc_engine *e, env_t *v, int action) {
       break;
     }
     case ORC_REP_TURTLE: { /* reps/turtle_rep.py:87-107, _dirs :14 on (row, col), no wrap (:20) */
+      /* ndim == 3: the same lines run on the 3-D map.  _dirs holds 2-tuples (:14), so `for i, d in enumerate(_dirs[a])`
+       * (:90-101) moves and clamps axes 0 and 1 only; pos[2] keeps the value drawn at reset (:43) for the whole episode.
+       * The write `_map[tuple(pos)]` (:103-105) lands at the C-order cell of all three coordinates, which is ravel(). */
       static const int DR[4] = {-1, 1, 0, 0}, DC[4] = {0, 0, -1, 1};
       if (action < 4) {
         int r = v->pos[0] + DR[action], c = v->pos[1] + DC[action];
@@ -503,6 +506,17 @@ static int base_update(const orc_engine *e, env_t *v, int action) {
       break;
     }
     case ORC_REP_WIDE: { /* wrappers.py:304-323 ActionMap.step + reps/wide_rep.py:40-45 (Q4: transposed) */
+      if (cfg->ndim == 3) {
+        /* 3-D: the reference's ActionMap wrapper is 2-D only; the 3-D env takes the MultiDiscrete (d0, d1, d2, n_tiles) of
+         * wide_rep.py get_action_space directly, and wide_rep.py:40-45 indexes `_map[tuple(action[:-1])]`: no
+         * transposition.  The engine's int is the C-order flat index over (d0, d1, d2, n_tiles) (README "The 3-D maze under
+         * turtle and wide"; tools/gen_golden_3d_reps.py ref_action).  _pos = action[:-1] (:41). */
+        int cell = action / e->n_tiles, t = action % e->n_tiles;
+        unravel(cfg, cell, v->pos);
+        change = v->grid[cell] != (uint8_t)t;
+        v->grid[cell] = (uint8_t)t;
+        break;
+      }
       int h = cfg->dims[0], w = cfg->dims[1], dim = e->n_tiles;
       int y = action / (w * dim), x = (action / dim) % w, t = action % dim;
       (void)h;
@@ -582,6 +596,7 @@ static void env_reset(const orc_engine *e, env_t *v, const uint8_t *init_grid, c
     for (int t = 0; t < nt; t++) total += probs[t];                      /* helper.py:527-536 */
     for (int t = 0; t < nt; t++) probs[t] /= total;
     v->pos[0] = v->pos[1] = v->pos[2] = 0;
+    /* (ndim == 3: `[int(random() * i) for i in dims]`, turtle_rep.py:43 -- three draws in axis order, before the map) */
     if (cfg->representation == ORC_REP_TURTLE) /* turtle_rep.py:31-44: position drawn BEFORE the map */
       for (int d = 0; d < cfg->ndim; d++) v->pos[d] = (int)(pcg64_double(&v->rng_rep) * cfg->dims[d]);
     /* Generator.choice(n, size=dims, p): cdf = cumsum(p); cdf /= cdf[-1];
@@ -620,6 +635,7 @@ static void env_reset(const orc_engine *e, env_t *v, const uint8_t *init_grid, c
  * ---------------------------------------------------------------------------------------------- */
 int64_t orc_obs_size(const orc_engine *e) {
   const orc_config *c = &e->cfg;
+  if (c->representation == ORC_REP_WIDE && c->ndim == 3) return (int64_t)e->n_cells * (e->n_tiles + 1); /* + path overlay */
   if (c->representation == ORC_REP_WIDE) return (int64_t)e->n_cells * e->n_tiles;
   int64_t n = 1;
   for (int d = 0; d < c->ndim; d++) n *= c->obs_window[d];
@@ -633,6 +649,22 @@ int64_t orc_obs_size(const orc_engine *e) {
 static void encode_obs(const orc_engine *e, const env_t *v, uint8_t *out, int show_path) {
   const orc_config *c = &e->cfg;
   memset(out, 0, (size_t)orc_obs_size(e));
+  if (c->representation == ORC_REP_WIDE && c->ndim == 3) {
+    /* 3-D wide: the whole map, one-hot over AIR, DIRT and the path overlay ([d0, d1, d2, 3]); no crop, no out-of-bounds
+     * channel.  The overlay follows the narrow 3-D branch below: the reference's transposed [x][y][z] write
+     * (minecraft_3D_maze_prob.py:84-93), out-of-range tiles skipped on non-cubic maps. */
+    for (int i = 0; i < e->n_cells; i++) out[(size_t)i * (e->n_tiles + 1) + v->grid[i]] = 1;
+    if (show_path)
+      for (int k = 0; k < v->path_len; k++) {
+        int x = v->path_xyz[3 * k], y = v->path_xyz[3 * k + 1], z = v->path_xyz[3 * k + 2];
+        if (x < c->dims[0] && y < c->dims[1] && z < c->dims[2]) {
+          uint8_t *o = out + (size_t)((x * c->dims[1] + y) * c->dims[2] + z) * (e->n_tiles + 1);
+          memset(o, 0, (size_t)e->n_tiles + 1);
+          o[e->n_tiles] = 1;
+        }
+      }
+    return;
+  }
   if (c->representation == ORC_REP_WIDE) {
     for (int i = 0; i < e->n_cells; i++) out[(size_t)i * e->n_tiles + v->grid[i]] = 1;
     return;
@@ -652,6 +684,8 @@ static void encode_obs(const orc_engine *e, const env_t *v, uint8_t *out, int sh
           out[((size_t)i * ow + j) * C + e->n_tiles + 1] = v->static_b[r * (c->dims[1] + 2) + q];
       }
   } else {
+    /* (narrow and turtle alike: the window of obs_window cells starts at pos - obs_window / 2 on each of the three axes,
+     * turtle's pos being wherever its moves left it, third coordinate included) */
     /* 3-D: the reference's image wrappers raise on this problem; this follows their
      * intent: cropped window, channel 0 = OOB, 1..n = tiles, n+1 = path overlay written at the
      * reference's transposed [x][y][z] indices (minecraft_3D_maze_prob.py:84-93). */

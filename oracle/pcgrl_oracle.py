@@ -145,6 +145,8 @@ def make_config(problem, representation, map_shape, obs_window=None, weights=Non
     ndim = len(map_shape)
     if obs_window is None:
         obs_window = map_shape if representation == "wide" else tuple(2 * s for s in map_shape)
+    if ndim == 3 and representation == "wide" and tuple(int(w) for w in obs_window) != map_shape:
+        raise ValueError(f"3-D wide observes the whole map: obs_window {tuple(obs_window)} != map_shape {map_shape}")
     if weights is None:
         weights = DEFAULT_WEIGHTS[problem]
     keys = STAT_KEYS[problem]
@@ -216,8 +218,8 @@ class OracleVecEnv:
 
     @property
     def obs_shape(self):
-        if self.representation == "wide":
-            return self.map_shape + (N_TILES[self.problem],)
+        if self.representation == "wide":  # (3-D: AIR, DIRT and the path overlay)
+            return self.map_shape + (N_TILES[self.problem] + (1 if len(self.map_shape) == 3 else 0),)
         ow = tuple(int(self.cfg.obs_window[d]) for d in range(len(self.map_shape)))
         extra = (1 if self.problem == "minecraft_3D_maze" else 0) + (1 if self.cfg.static_tiles else 0)
         return ow + (N_TILES[self.problem] + 1 + extra,)

@@ -7,6 +7,12 @@ wrappers (static tiles / action patch) and optional controls from the space the 
 stats / reward / done at every step and observations / full state every few steps (bit-exact; rewards to 1e-6 / 1e-9).
 A failing case prints its one-line description, which `--case '<json>'` replays.
 
+The generator has a version (`gen`).  Generation 1 is the generator as it stood before the 3-D maze had other
+representations than narrow; its draws are frozen (tests/golden/fuzz/gen1_seed20261002_250.jsonl).  Generation 2 adds, for
+minecraft_3D_maze, the turtle and wide representations (the oracle is pinned on them by tests/test_oracle_3d_reps.py) and
+asynchronous stepping (mode "ready") of plain narrow cases, and for every problem the tile-code observation form
+(obs_format "codes").
+
 Checker-side script (it imports oracle/): lives under tests/, is not collected by pytest; tests/test_gpu_parity.py runs
 a short fixed-seed sweep of it.  On the GPU box:  python tests/fuzz_parity.py --cases 200 --seed 1
 """
@@ -32,9 +38,17 @@ STAT_KEYS = {"binary": ["regions", "path-length"],
              "minecraft_3D_maze": ["regions", "path-length", "n_jump"]}
 
 
-def draw_case(rng):
-    """one random configuration (a JSON-able dict) the engine accepts"""
-    case = _draw_case(rng)
+GENERATIONS = (1, 2)
+# the fixed-seed sweep of generation 2 (tests/test_gpu_parity.py::test_fuzz_sweep_gen2_fixed_seed): the seed is one whose first
+# `cases` draws meet the floors of tests/test_host_cpu.py::test_fuzzer_generations; the count is set by time
+GEN2_SWEEP = dict(seed=20261035, cases=250)
+
+
+def draw_case(rng, gen=2):
+    """one random configuration (a JSON-able dict) the engine accepts; gen=1 draws what the first generation drew, draw
+    for draw (every draw of a later generation sits behind `gen >= ...`)"""
+    assert gen in GENERATIONS, gen
+    case = _draw_case(rng, gen)
     kw = case["kw"]
     if rng.random() < 0.25:
         kw["weights"] = {k: int(rng.integers(0, 6)) for k in STAT_KEYS[case["problem"]]}
@@ -56,22 +70,40 @@ def draw_case(rng):
             and rng.random() < 0.45):
         case["mode"] = "ready"
         case["budget"] = int(rng.choice([1, 3, 8, 16, 64, 400, 100000]))
+    if gen >= 2:
+        # asynchronous stepping of the 3-D maze: narrow without controls, any shape (what pcgrl_set_solver_budget accepts,
+        # include/pcgrl_amd_async3d.h); the budget counts search trips per env and launch
+        if case["problem"] == "minecraft_3D_maze" and case["rep"] == "narrow" and "controls" not in kw and rng.random() < 0.3:
+            case["mode"] = "ready"
+            case["budget"] = int(rng.choice([1, 2, 4, 16, 64, 100000]))
+        # the tile-code observation form, on the cases run_case / run_ready_case run (the adapters have fixed tests for it)
+        if case.get("mode") not in ("adapter", "gym") and rng.random() < 0.15:
+            case["obs_format"] = "codes"
     return case
 
 
-def _draw_case(rng):
-    problem = str(rng.choice(["binary", "zelda", "sokoban", "minecraft_3D_maze"], p=[0.35, 0.3, 0.15, 0.2]))
+def _draw_case(rng, gen):
+    # (generation 2 is about the 3-D maze: twice its share, the 2-D problems in their old proportions)
+    problem = str(rng.choice(["binary", "zelda", "sokoban", "minecraft_3D_maze"],
+                             p=[0.35, 0.3, 0.15, 0.2] if gen < 2 else [0.2625, 0.225, 0.1125, 0.4]))
     case = dict(problem=problem, kw={})
     kw = case["kw"]
     if problem == "minecraft_3D_maze":
-        case["rep"] = "narrow"
+        case["rep"] = str(rng.choice(["narrow", "turtle", "wide"], p=[0.4, 0.3, 0.3])) if gen >= 2 else "narrow"
         big = rng.random() < 0.25
         hi = 16 if big else 8
         shape = [int(rng.integers(1, hi + 1)) for _ in range(3)]
+        if gen >= 2 and case["rep"] != "narrow" and rng.random() < 0.2:
+            # maps of a few cells: axes of length 1, wide observation rows of 3 ... 81 bytes (the wide store path writes
+            # 16-byte words with single bytes at either end: rows below one word are all "ends")
+            shape = [int(rng.integers(1, 4)) for _ in range(3)]
         if rng.random() < 0.2:  # BASELINE's shape: the compile-time 7^3 / 14^3 kernels
             shape = [7, 7, 7]
         case["shape"] = shape
-        if rng.random() < 0.4:  # any window whose volume is a multiple of 4
+        # (wide: the whole map is the observation, pcgrl_create refuses any other window; its 3 * cells bytes per env are
+        # below the 32 * cells of the default narrow window, so the n_envs bound below keeps a case's observation bytes
+        # within what the narrow cases already reach)
+        if case["rep"] != "wide" and rng.random() < 0.4:  # any window whose volume is a multiple of 4
             ow = [int(rng.integers(1, (3 * s + 6) if rng.random() < 0.1 else (2 * s + 3))) for s in shape]
             ow[2] += (-ow[2]) % 4 if (ow[0] * ow[1] * ow[2]) % 4 else 0
             kw["obs_window"] = ow
@@ -174,6 +206,13 @@ def run_case(case, seed, verbose=False):
     ekw = dict(kw)
     if controls:
         ekw["reward_dtype"] = torch.float64
+    codes = case.get("obs_format", "onehot") == "codes"
+    if codes:  # every call of the engine hands out tile codes (VecPcgrlEnv._route_obs); compared as the one-hot image they mean
+        ekw["obs_format"] = "codes"
+
+    def img(o):
+        from control_pcgrl_amd.vec_env import codes_to_onehot
+        return (codes_to_onehot(o, env) if codes else o).cpu().numpy()
 
     def make_engine():
         return VecPcgrlEnv(problem, rep, shape, n, seeds=seeds, auto_reset=auto, **ekw)
@@ -288,7 +327,7 @@ def run_case(case, seed, verbose=False):
         env.set_target_resampling(True, resample)
     before_resets()
     obs, info = env.reset()
-    assert np.array_equal(obs.cpu().numpy(), orc.reset()), "reset observation"
+    assert np.array_equal(img(obs), orc.reset()), "reset observation"
     after_resets(np.ones(n, bool))
     check_ctrl("after reset")
     full_every = int(rng.integers(3, 30))
@@ -320,7 +359,7 @@ def run_case(case, seed, verbose=False):
                 assert np.array_equal(done.cpu().numpy(), odone), f"done {what}"
                 check_ctrl(what)
                 if want:
-                    assert np.array_equal(obs.cpu().numpy(), oobs), f"obs {what}"
+                    assert np.array_equal(img(obs), oobs), f"obs {what}"
                     check_state(what)
                 t += 1
         elif ev == "rollout":
@@ -338,7 +377,7 @@ def run_case(case, seed, verbose=False):
                 env._L.pcgrl_set_rollout_form(env._h, -1)
             case.setdefault("_trace", []).append(f"rollout_form={form}")
             rew, done, stats = rew.cpu().numpy().astype(np.float64), done.cpu().numpy(), stats.cpu().numpy()
-            obs = None if obs is None else obs.cpu().numpy()
+            obs = None if obs is None else img(obs)
             for k in range(K):
                 oobs, orew, odone, ostats = orc_step(a[k].numpy(), True)
                 if not check_stats(stats[k], ostats, odone, f"{what} step {k}/{K}"):
@@ -355,7 +394,7 @@ def run_case(case, seed, verbose=False):
         elif ev in ("update_refresh", "update_step"):
             for _ in range(int(rng.integers(1, 5))):
                 a = draw_actions(t)
-                assert np.array_equal(env.update(a.to(env.device)).cpu().numpy(), orc.update(a.numpy())), f"update obs {what}"
+                assert np.array_equal(img(env.update(a.to(env.device))), orc.update(a.numpy())), f"update obs {what}"
             if ev == "update_refresh":
                 if not check_stats(env.refresh_stats().cpu().numpy(), orc.refresh_stats(), None, what):
                     return -2
@@ -371,14 +410,14 @@ def run_case(case, seed, verbose=False):
             env.check_errors()
             env.close()
             env = env2
-            assert np.array_equal(env.observe().cpu().numpy(), orc.observe()), f"obs {what}"
+            assert np.array_equal(img(env.observe()), orc.observe()), f"obs {what}"
             check_state(what)
             t += 1
         elif ev == "masked_reset":
             mask = (rng.random(n) < rng.random()).astype(np.uint8)
             before_resets()
             obs, _ = env.reset(mask=mask)
-            assert np.array_equal(obs.cpu().numpy(), orc.reset(mask=mask)), f"obs {what}"
+            assert np.array_equal(img(obs), orc.reset(mask=mask)), f"obs {what}"
             after_resets(mask)
             check_ctrl(what)
             check_state(what)
@@ -389,7 +428,7 @@ def run_case(case, seed, verbose=False):
             pos = np.stack([rng.integers(0, s, size=n) for s in shape], axis=1).astype(np.int32)
             before_resets()
             obs, _ = env.reset(mask=mask, init_grids=grids, init_pos=pos)
-            assert np.array_equal(obs.cpu().numpy(), orc.reset(mask=mask, init_grids=grids, init_pos=pos)), f"obs {what}"
+            assert np.array_equal(img(obs), orc.reset(mask=mask, init_grids=grids, init_pos=pos)), f"obs {what}"
             after_resets(mask)
             if not check_stats(env.get_state().stats.cpu().numpy(), orc.get_state()["stats"], None, what):
                 return -2
@@ -415,7 +454,7 @@ def run_case(case, seed, verbose=False):
                     return -2
                 assert np.max(np.abs(rew.cpu().numpy().astype(np.float64) - orew)) <= tol, f"reward {what} replay {r}/{R}"
                 assert np.array_equal(done.cpu().numpy(), odone), f"done {what} replay {r}/{R}"
-                assert np.array_equal(obs.cpu().numpy(), oobs), f"obs {what} replay {r}/{R}"
+                assert np.array_equal(img(obs), oobs), f"obs {what} replay {r}/{R}"
             check_ctrl(what)
             check_state(what)
             del graph
@@ -445,7 +484,7 @@ def run_case(case, seed, verbose=False):
             orc.set_static(static_prob=sp, n_static_walls=nw, eval_mode=ev_mode)
             t += 1
         else:
-            assert np.array_equal(env.observe().cpu().numpy(), orc.observe()), f"obs {what}"
+            assert np.array_equal(img(env.observe()), orc.observe()), f"obs {what}"
             t += 1
     le, ole = env.last_episode(), orc.last_episode()
     assert np.array_equal(le.n_episodes.cpu().numpy(), ole["n_episodes"]), "episode counts"
@@ -464,10 +503,12 @@ def run_case(case, seed, verbose=False):
 
 
 def run_ready_case(case, seed):
-    """sokoban through pcgrl_set_solver_budget / pcgrl_step_ready: the device solver works to a budget per launch and parks
-    what it could not finish; busy envs ignore their actions.  The oracle steps an env exactly when the engine reports an
-    emitted transition, with the action the env consumed; resets (masked, injected playable levels) abandon steps in flight;
-    a checkpoint into a fresh engine loses the parked searches (they restart) but not the pending steps."""
+    """sokoban / the 3-D maze under narrow through pcgrl_set_solver_budget / pcgrl_step_ready: the device solver (sokoban) or
+    the path searches (3-D maze, include/pcgrl_amd_async3d.h) work to a budget per launch and park what they could not finish;
+    busy envs ignore their actions.  The oracle steps an env exactly when the engine reports an emitted transition, with the
+    action the env consumed; resets (masked, injected maps -- sokoban: playable levels among them) abandon steps in flight; a
+    checkpoint into a fresh engine loses the parked searches (they restart) but not the pending steps.
+    Returns (emitted transitions, launches after which an env was busy)."""
     import torch
     import pcgrl_oracle as po  # (checker)
     from control_pcgrl_amd import VecPcgrlEnv
@@ -476,22 +517,28 @@ def run_ready_case(case, seed):
     kw = {k: (tuple(v) if k == "obs_window" else v) for k, v in case["kw"].items()}
     auto, budget = bool(case.get("auto_reset", True)), int(case["budget"])
     seeds = seed + np.arange(n)
+    codes = case.get("obs_format", "onehot") == "codes"
+    ekw = dict(kw, obs_format="codes") if codes else kw
 
     def make_engine():
-        e = VecPcgrlEnv(problem, rep, shape, n, seeds=seeds, auto_reset=auto, **kw)
+        e = VecPcgrlEnv(problem, rep, shape, n, seeds=seeds, auto_reset=auto, **ekw)
         e.set_solver_budget(budget)
         return e
+
+    def img(o):
+        from control_pcgrl_amd.vec_env import codes_to_onehot
+        return (codes_to_onehot(o, env) if codes else o).cpu().numpy()
 
     env = make_engine()
     orc = po.OracleVecEnv(problem, rep, shape, n, seeds=seeds, threads=8, **kw)
     rng = np.random.default_rng(seed)
     g = torch.Generator().manual_seed(seed)
     obs, _ = env.reset()
-    assert np.array_equal(obs.cpu().numpy(), orc.reset()), "reset observation"
+    assert np.array_equal(img(obs), orc.reset()), "reset observation"
     busy = env.env_busy().cpu().numpy().astype(bool)
     pend, has_pend = np.zeros(n, np.int32), np.zeros(n, bool)
     trace = case.setdefault("_trace", [])
-    emitted_total, t = 0, 0
+    emitted_total, busy_launches, t = 0, 0, 0
     while t < T:
         ev = str(rng.choice(["step", "inject", "masked_reset", "swap"], p=[0.8, 0.1, 0.05, 0.05]))
         what = f"@ {t} ({ev})"
@@ -499,7 +546,7 @@ def run_ready_case(case, seed):
         if ev == "step":
             for _ in range(int(rng.integers(1, 12))):
                 a = torch.randint(0, env.num_actions, (n,), generator=g, dtype=torch.int32).numpy()
-                if rng.random() < 0.5:  # mostly floor / wall edits: playable levels stay playable for a while
+                if problem == "sokoban" and rng.random() < 0.5:  # mostly floor / wall edits: playable levels stay playable for a while
                     a = (a // 5) * 5 + (a % 2)
                 consume = ~busy
                 pend[consume] = a[consume]
@@ -516,9 +563,10 @@ def run_ready_case(case, seed):
                         raise AssertionError(f"stats {what}: env {e} got {got[e].tolist()} want {ostats[e].tolist()} (budget {budget})")
                     assert np.abs(rew.cpu().numpy()[emitted] - orew[emitted]).max() <= 1e-6, f"reward {what}"
                     assert np.array_equal(done.cpu().numpy()[emitted], odone[emitted]), f"done {what}"
-                    assert np.array_equal(obs.cpu().numpy()[emitted], oobs[emitted]), f"obs {what}"
+                    assert np.array_equal(img(obs)[emitted], oobs[emitted]), f"obs {what}"
                 has_pend[emitted] = False
                 busy = (status & 2) != 0
+                busy_launches += int(busy.any())
                 assert not (~busy & has_pend).any(), f"an idle env still owes a transition {what}"
                 emitted_total += int(emitted.sum())
                 t += 1
@@ -532,7 +580,7 @@ def run_ready_case(case, seed):
             else:
                 obs, _ = env.reset(mask=mask)
                 want = orc.reset(mask=mask)
-            assert np.array_equal(obs.cpu().numpy(), want), f"obs {what}"
+            assert np.array_equal(img(obs), want), f"obs {what}"
             has_pend[mask != 0] = False  # steps in flight are abandoned with the old map
             busy = env.env_busy().cpu().numpy().astype(bool)
             t += 1
@@ -544,7 +592,7 @@ def run_ready_case(case, seed):
             env.close()
             env = env2
             assert np.array_equal(env.env_busy().cpu().numpy().astype(bool), busy), f"busy flags {what}"
-            assert np.array_equal(env.observe().cpu().numpy(), orc.observe()), f"obs {what}"
+            assert np.array_equal(img(env.observe()), orc.observe()), f"obs {what}"
             t += 1
         st, ost = env.get_state(), orc.get_state()
         assert np.array_equal(st.grids.cpu().numpy().reshape(n, -1), ost["grids"]), f"grids {what}"
@@ -556,7 +604,7 @@ def run_ready_case(case, seed):
     assert np.array_equal(le.final_stats.cpu().numpy(), ole["final_stats"]), "final stats"
     env.check_errors()
     env.close()
-    return emitted_total
+    return emitted_total, busy_launches
 
 
 def _final_check(vec, problem):
@@ -720,22 +768,36 @@ def run_gym_case(case, seed):
     return int(orc.last_episode()["n_episodes"].sum()) if ok else -2
 
 
-def sweep(n_cases, seed, verbose=True, stop_on_fail=True, budget_s=None, only=None):
+RUNNERS = {"adapter": run_adapter_case, "gym": run_gym_case, "ready": run_ready_case}
+
+
+def run_any(case, seed):
+    """runs `case` by its mode; returns (episodes or emitted transitions, busy launches or None)"""
+    out = RUNNERS.get(case.get("mode"), run_case)(case, seed)
+    return out if isinstance(out, tuple) else (out, None)
+
+
+def sweep(n_cases, seed, verbose=True, stop_on_fail=True, budget_s=None, only=None, gen=2):
     rng = np.random.default_rng(seed)
     t0 = time.time()
     failures, refused = [], []
+    sweep.ran = 0
+    sweep.ready_busy = {}  # problem -> launches of its ready cases after which an env was busy (0: parking never happened)
     for i in range(n_cases):
-        case = draw_case(rng)
+        case = draw_case(rng, gen)
         cs = int(rng.integers(0, 1 << 30))
         if only and case["problem"] not in only:
             continue
         line = json.dumps(dict(case, seed=cs))
         t1 = time.time()
         try:
-            eps = {"adapter": run_adapter_case, "gym": run_gym_case, "ready": run_ready_case}.get(case.get("mode"), run_case)(case, cs)
+            sweep.ran += 1
+            eps, nbusy = run_any(case, cs)
             case.pop("_trace", None)
+            if nbusy is not None:
+                sweep.ready_busy[case["problem"]] = sweep.ready_busy.get(case["problem"], 0) + nbusy
             if verbose:
-                print(f"ok   {i:4d} {time.time() - t1:6.1f}s eps={eps:5d} {line}", flush=True)
+                print(f"ok   {i:4d} {time.time() - t1:6.1f}s eps={eps:5d}{'' if nbusy is None else f' busy={nbusy}'} {line}", flush=True)
         except NotImplementedError as e:
             # The engine REFUSED (PCGRL_EUNSUPPORTED: a stated limit of the device solver / the 3-D search was met at run time,
             # reported, never silent).  Not a parity failure -- nothing wrong was handed out -- and counted on its own: the
@@ -762,6 +824,8 @@ if __name__ == "__main__":
     ap.add_argument("--keep-going", action="store_true")
     ap.add_argument("--case", type=str, default=None, help="replay one case (the JSON a failure printed)")
     ap.add_argument("--dry", action="store_true", help="only print the drawn cases (no GPU needed)")
+    ap.add_argument("--gen", type=int, default=2, choices=GENERATIONS, help="generator version (1: as before the 3-D turtle / wide / "
+                    "ready and codes cases; its draws are frozen)")
     ap.add_argument("--only", type=str, default=None, help="comma-separated problems to keep (the others are drawn and skipped)")
     ap.add_argument("--max-refused", type=int, default=-1,
                     help="refusals (PCGRL_EUNSUPPORTED at run time) tolerated before the campaign FAILS (exit code 2); default: "
@@ -771,18 +835,20 @@ if __name__ == "__main__":
     if a.dry:
         r = np.random.default_rng(a.seed)
         for _ in range(a.cases):
-            c = draw_case(r)
+            c = draw_case(r, a.gen)
             print(json.dumps(dict(c, seed=int(r.integers(0, 1 << 30)))))
         sys.exit(0)
     if a.case:
         c = json.loads(a.case)
         s = c.pop("seed")
         try:
-            print("episodes:", {"adapter": run_adapter_case, "gym": run_gym_case, "ready": run_ready_case}.get(c.get("mode"), run_case)(c, s))
+            print("episodes, busy launches:", run_any(c, s))
         finally:
             print("events:", " ".join(c.get("_trace", [])))
         sys.exit(0)
-    f = sweep(a.cases, a.seed, stop_on_fail=not a.keep_going, budget_s=a.budget_s, only=a.only.split(",") if a.only else None)
+    f = sweep(a.cases, a.seed, stop_on_fail=not a.keep_going, budget_s=a.budget_s, only=a.only.split(",") if a.only else None,
+              gen=a.gen)
     limit = a.max_refused if a.max_refused >= 0 else max(2, a.cases // 500)
-    print(f"{len(f)} failure(s), {len(sweep.refused)} refused (reported limits, see REFUSED lines; tolerated: {limit})")
+    print(f"{sweep.ran} case(s) run (gen {a.gen}, seed {a.seed}), {len(f)} failure(s), {len(sweep.refused)} refused (reported limits, "
+          f"see REFUSED lines; tolerated: {limit}); busy launches of ready cases: {sweep.ready_busy}")
     sys.exit(1 if f else (2 if len(sweep.refused) > limit else 0))

@@ -1678,9 +1678,25 @@ def test_fuzz_sweep_fixed_seed():
     """tests/fuzz_parity.py: 250 random supported configurations (problem x representation x map shape x window x change
     budget x wrappers x controls) against the oracle, every step.  Longer sweeps: python tests/fuzz_parity.py --cases N"""
     import fuzz_parity
-    failures = fuzz_parity.sweep(250, 20261002, verbose=False, stop_on_fail=False)
+    failures = fuzz_parity.sweep(250, 20261002, verbose=False, stop_on_fail=False, gen=1)  # (the generator as it stood: frozen)
     assert not failures, failures[:3]
     assert not fuzz_parity.sweep.refused, fuzz_parity.sweep.refused[:3]  # nothing the generator draws is refused at run time
+
+
+def test_fuzz_sweep_gen2_fixed_seed():
+    """the generator's second generation: next to what the first draws, the 3-D maze under turtle and wide (maps of a few
+    cells and axes of length 1 among them), its asynchronous stepping under narrow, and the tile-code observation form on
+    every problem.  The case count (fuzz_parity.GEN2_SWEEP) is the largest multiple of 50 whose sweep takes no longer than
+    the 250 cases of test_fuzz_sweep_fixed_seed on an MI355X (DESIGN section 2 has both durations);
+    tests/test_host_cpu.py::test_fuzzer_generations checks what it draws."""
+    import fuzz_parity
+    n_cases, seed = fuzz_parity.GEN2_SWEEP["cases"], fuzz_parity.GEN2_SWEEP["seed"]
+    failures = fuzz_parity.sweep(n_cases, seed, verbose=False, stop_on_fail=False, gen=2)
+    assert not failures, failures[:3]
+    assert not fuzz_parity.sweep.refused, fuzz_parity.sweep.refused[:3]
+    assert fuzz_parity.sweep.ran == n_cases
+    # the 3-D ready cases parked searches: without a launch that left an env busy, asynchronous stepping was never exercised
+    assert fuzz_parity.sweep.ready_busy.get("minecraft_3D_maze", 0) >= 1, fuzz_parity.sweep.ready_busy
 
 
 def test_injected_maps_with_action_patch_ignore_init_pos():

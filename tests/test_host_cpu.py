@@ -92,8 +92,6 @@ def test_sub_batched_env_validates_the_split():
 def test_host_tables_match_oracle_tables(problem, shape):
     from control_pcgrl_amd.vec_env import build_config
     for rep in ("narrow", "turtle", "wide"):
-        if problem == "minecraft_3D_maze" and rep != "narrow":
-            continue
         c, spec, ow = build_config(problem, rep, shape)
         o = po.make_config(problem, rep, shape)
         for f in ("problem", "representation", "ndim", "max_iterations", "max_changes", "n_stats", "solver_power"):
@@ -246,33 +244,96 @@ def test_empty_static_target_range_is_refused_like_the_reference():
 
 
 def test_fuzzer_draws_only_configurations_the_engine_validates():
-    """tests/fuzz_parity.py's generator stays inside the accepted configuration space: every drawn case builds a config on
-    the host and passes pcgrl_create's validation (which runs before any HIP call: without a GPU the call then fails
-    with PCGRL_EHIP, never EINVAL / EUNSUPPORTED), or is refused by host and oracle alike (empty target ranges)."""
+    """tests/fuzz_parity.py's generator stays inside the accepted configuration space, in both of its generations: every
+    drawn case builds a config on the host and passes pcgrl_create's validation (which runs before any HIP call: without a
+    GPU the call then fails with PCGRL_EHIP, never EINVAL / EUNSUPPORTED), or is refused by host and oracle alike (empty
+    target ranges)."""
     import ctypes as C
     import fuzz_parity
     from control_pcgrl_amd import _lib
     from control_pcgrl_amd.vec_env import build_config
+    assert fuzz_parity.GENERATIONS == (1, 2)
     L = _lib.lib()
-    rng = np.random.default_rng(12345)
-    refused = 0
-    for i in range(400):
-        case = fuzz_parity.draw_case(rng)
-        kw = {k: (tuple(v) if k == "obs_window" else v) for k, v in case["kw"].items()}
-        try:
-            cfg, _, _ = build_config(case["problem"], case["rep"], tuple(case["shape"]), **kw)
-        except ValueError:
-            with pytest.raises(ValueError):
-                po.make_config(case["problem"], case["rep"], tuple(case["shape"]), **kw)
-            refused += 1
-            continue
-        po.make_config(case["problem"], case["rep"], tuple(case["shape"]), **kw)
-        h = C.c_void_p()
-        rc = L.pcgrl_create(C.byref(cfg), case["n_envs"], 0, C.byref(h))
-        assert rc not in (1, 2), (case, L.pcgrl_last_error())
-        if rc == 0:  # (a GPU is present after all)
-            L.pcgrl_destroy(h)
-    assert refused < 40
+    for gen in fuzz_parity.GENERATIONS:
+        rng = np.random.default_rng(12345)
+        refused = 0
+        for i in range(400):
+            case = fuzz_parity.draw_case(rng, gen)
+            kw = {k: (tuple(v) if k == "obs_window" else v) for k, v in case["kw"].items()}
+            try:
+                cfg, _, _ = build_config(case["problem"], case["rep"], tuple(case["shape"]), **kw)
+            except ValueError:
+                with pytest.raises(ValueError):
+                    po.make_config(case["problem"], case["rep"], tuple(case["shape"]), **kw)
+                refused += 1
+                continue
+            po.make_config(case["problem"], case["rep"], tuple(case["shape"]), **kw)
+            h = C.c_void_p()
+            rc = L.pcgrl_create(C.byref(cfg), case["n_envs"], 0, C.byref(h))
+            assert rc not in (1, 2), (gen, case, L.pcgrl_last_error())
+            if rc == 0:  # (a GPU is present after all)
+                L.pcgrl_destroy(h)
+        assert refused < 40, gen
+
+
+def test_fuzzer_generations():
+    """the generator's versions: generation 1 is frozen (its fixed-seed GPU sweep runs the cases it always ran), and
+    generation 2 draws what it was added for, in the numbers its fixed-seed GPU sweep relies on; every 3-D turtle / wide
+    case it draws runs on the oracle with observations of the engine's shape"""
+    import json
+    import fuzz_parity
+    from control_pcgrl_amd.vec_env import build_config, obs_shape_for
+
+    def drawn(gen, seed, n):
+        rng = np.random.default_rng(seed)
+        out = []
+        for _ in range(n):  # (what `--dry` prints and sweep() runs: a case, then its seed)
+            c = fuzz_parity.draw_case(rng, gen)
+            out.append(dict(c, seed=int(rng.integers(0, 1 << 30))))
+        return out
+
+    with open(os.path.join(ROOT, "tests", "golden", "fuzz", "gen1_seed20261002_250.jsonl")) as f:
+        frozen = f.read().splitlines()
+    gen1 = drawn(1, 20261002, 250)
+    assert len(frozen) == 250 and [json.dumps(c) for c in gen1] == frozen
+    assert not any(c.get("obs_format") or (c["problem"] == "minecraft_3D_maze" and (c["rep"] != "narrow" or c["mode"] == "ready"))
+                   for c in gen1)
+
+    cases = drawn(2, fuzz_parity.GEN2_SWEEP["seed"], fuzz_parity.GEN2_SWEEP["cases"])
+    assert len(cases) % 50 == 0
+    d3 = [c for c in cases if c["problem"] == "minecraft_3D_maze"]
+    reps3 = [c for c in d3 if c["rep"] in ("turtle", "wide")]
+    wide = [c for c in d3 if c["rep"] == "wide"]
+    ready = [c for c in d3 if c.get("mode") == "ready"]
+    assert len([c for c in d3 if c["rep"] == "turtle"]) >= 8 and len(wide) >= 8 and len(ready) >= 8
+    assert all(c["rep"] == "narrow" and "controls" not in c["kw"] and c["budget"] >= 1 for c in ready)
+    assert all("obs_window" not in c["kw"] for c in wide)
+    assert len([c for c in wide if int(np.prod(c["shape"])) * 3 < 16]) >= 3  # observation rows shorter than one 16-byte word
+    assert len([c for c in reps3 if min(c["shape"]) == 1]) >= 3
+    assert len([c for c in cases if c.get("obs_format") == "codes"]) >= 15
+    assert all(c.get("mode") not in ("adapter", "gym") for c in cases if c.get("obs_format") == "codes")
+    assert {c.get("mode") for c in reps3} >= {"step", "mixed"}
+
+    more = drawn(2, 7, 600)  # (codes are drawn for ready cases of both problems, too)
+    assert {c["problem"] for c in more if c.get("mode") == "ready" and c.get("obs_format") == "codes"} == {"sokoban", "minecraft_3D_maze"}
+    more = [c for c in more if c["problem"] == "minecraft_3D_maze" and c["rep"] in ("turtle", "wide")]
+    assert {c.get("mode") for c in more} >= {"step", "mixed", "adapter", "gym"} and len(more) > 100
+    for c in reps3 + more:
+        rep, shape = c["rep"], tuple(c["shape"])
+        kw = {k: (tuple(v) if k == "obs_window" else v) for k, v in c["kw"].items()}
+        cfg, spec, ow = build_config(c["problem"], rep, shape, **kw)
+        n = min(c["n_envs"], 4)
+        orc = po.OracleVecEnv(c["problem"], rep, shape, n, seeds=c["seed"] + np.arange(n), **kw)
+        want = (n,) + obs_shape_for(cfg, spec, ow)
+        assert orc.reset().shape == want, c
+        rng = np.random.default_rng(c["seed"])
+        n_act = 6 if rep == "turtle" else int(np.prod(shape)) * 2
+        for t in range(20):
+            obs, rew, done, stats = orc.step(rng.integers(0, n_act, size=n), auto_reset=True)
+            assert obs.shape == want and obs.dtype == np.uint8 and (obs.sum(-1) == 1).all(), c
+            assert stats.shape == (n, 3) and np.isfinite(rew).all()
+        st = orc.get_state()
+        assert (st["pos"] >= 0).all() and (st["pos"] < np.array(shape)).all() and st["grids"].max() <= 1
 
 
 def test_bench_workload_tables_are_consistent():
