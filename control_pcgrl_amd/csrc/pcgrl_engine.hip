@@ -23,8 +23,10 @@
 #include "codes/pcgrl_codes.h"
 #include "reps3d/pcgrl_reps3d.h"  // the 3-D maze under turtle / wide
 #include "async3d/pcgrl_async3d.h"  // the 3-D maze (narrow) under a solver budget
+#include "paths/pcgrl_paths.h"      // solution paths of binary / zelda maps
 #include "../../include/pcgrl_amd_codes.h"
 #include "../../include/pcgrl_amd_async3d.h"
+#include "../../include/pcgrl_amd_paths.h"
 
 using namespace pcgrl;
 
@@ -1746,6 +1748,53 @@ int pcgrl_step_ready_codes(pcgrl_handle h, const int32_t *d_actions, int32_t aut
   if (rc != PCGRL_OK) return rc;
   ON_DEVICE(h->device);
   return onehot_to_codes(h, d_scratch, h->p.n_envs, d_codes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- solution paths
+// include/pcgrl_amd_paths.h; kernels in paths/pcgrl_paths.h
+int32_t pcgrl_path_capacity(pcgrl_handle h) {
+  if (!h) return -1;
+  const int cells = h->p.cfg.dims[0] * h->p.cfg.dims[1];
+  switch (h->p.cfg.problem) {
+    case PCGRL_PROB_BINARY: return cells;
+    case PCGRL_PROB_ZELDA: return 2 * cells;
+    default: return 0;  // (no path to hand out)
+  }
+}
+
+// n maps -- the engine's own (d_grids == nullptr, own) or the caller's -- through the path kernel
+static int paths_launch(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t cap, int16_t *d_path,
+                        int32_t *d_len, void *d_overlay, void *stream) {
+  if (!h || cap < 1 || n < 0 || (n > 0 && (!d_path || !d_len || (!own && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  const int prob = h->p.cfg.problem;
+  if (prob != PCGRL_PROB_BINARY && prob != PCGRL_PROB_ZELDA)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + (prob == PCGRL_PROB_SOKOBAN
+                                        ? ": sokoban's solution is an action list out of a transient search, not a path"
+                                        : ": the 3-D maze shows its path as the overlay channel of the observation"));
+  if (n == 0) return PCGRL_OK;
+  ON_DEVICE(h->device);
+  Params p = h->p;
+  p.n_envs = n;  // the kernel touches no per-env engine state but the tile planes
+  p.init_grids = d_grids;
+  PathArgs a;
+  a.path = d_path;
+  a.len = d_len;
+  a.overlay = (uint8_t *)d_overlay;
+  a.cap = cap;
+  a.from_grids = own ? 0 : 1;
+  a.ts = 0;
+  HIPCHK(launch_paths(p, h->lpe, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_paths(pcgrl_handle h, int32_t cap, int16_t *d_path, int32_t *d_len, uint8_t *d_overlay, void *stream) {
+  return paths_launch(h, "pcgrl_paths", true, h ? h->p.n_envs : 0, nullptr, cap, d_path, d_len, d_overlay, stream);
+}
+
+int pcgrl_paths_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t cap, int16_t *d_path, int32_t *d_len,
+                          uint8_t *d_overlay, void *stream) {
+  return paths_launch(h, "pcgrl_paths_for_grids", false, n, d_grids, cap, d_path, d_len, d_overlay, stream);
 }
 
 }  // extern "C"

@@ -166,6 +166,15 @@ class PcgrlGymEnv:
     def get_map(self):
         return self._vec.get_state().grids[0].cpu().numpy()
 
+    @property
+    def path_coords(self):
+        """The solution path of the current map, int32 [len, 2] (row, col): the reference's env.unwrapped._prob.path_coords
+        (binary_prob.py:152-158) / .path (zelda_ctrl_prob.py:153-165 with render_path)."""
+        p = self._vec.paths()
+        return p.coords[0, :int(p.length[0])].cpu().numpy().astype(np.int32)
+
+    path = path_coords
+
     def close(self):
         self._vec.close()
 

@@ -627,6 +627,38 @@ class VecPcgrlEnv:
                    "pcgrl_stats_for_grids_h")
         return out
 
+    # -- solution paths (include/pcgrl_amd_paths.h) ------------------------------------------------------------------
+    def _paths(self, n, grids, cap, overlay):
+        if cap is None:  # (a problem without paths reports 0: the call below is what refuses it)
+            cap = max(1, int(self._L.pcgrl_path_capacity(self._h)))
+        cap, dev = int(cap), self.device
+        out = SimpleNamespace(coords=torch.empty((n, cap, 2), dtype=torch.int16, device=dev),
+                              length=torch.empty(n, dtype=torch.int32, device=dev),
+                              overlay=torch.empty((n,) + self.map_shape, dtype=torch.uint8, device=dev) if overlay else None)
+        ov = out.overlay.data_ptr() if overlay else None
+        if grids is None:
+            _lib.check(self._L.pcgrl_paths(self._h, cap, out.coords.data_ptr(), out.length.data_ptr(), ov, self._stream()),
+                       "pcgrl_paths")
+        else:
+            _lib.check(self._L.pcgrl_paths_for_grids(self._h, n, grids.data_ptr(), cap, out.coords.data_ptr(),
+                                                     out.length.data_ptr(), ov, self._stream()), "pcgrl_paths_for_grids")
+        return out
+
+    def paths(self, cap=None, overlay=False):
+        """The solution path of every env's current map, as the reference keeps it for rendering (binary:
+        _prob.path_coords, binary_prob.py:152-158; zelda: _prob.path with render_path, zelda_ctrl_prob.py:153-165):
+          coords  int16 [N, cap, 2]  the first min(length, cap) cells as (row, col), then (-1, -1)
+          length  int32 [N]          the full length (binary: path-length + 1, or 0)
+          overlay uint8 [N, H, W]    1 on the path's cells (overlay=True), else None
+        cap=None: the longest path the map shape allows.  A function of the map alone (stale statistics do not matter);
+        one launch on the current stream, no host sync.  sokoban / the 3-D maze: NotImplementedError."""
+        return self._paths(self.num_envs, None, cap, overlay)
+
+    def paths_for_grids(self, grids, cap=None, overlay=False):
+        """paths() of caller maps (any number of them, uint8 tile ids of this env's problem and map shape)."""
+        g = torch.as_tensor(grids, device=self.device).to(torch.uint8).contiguous()
+        return self._paths(g.numel() // self.n_cells, g, cap, overlay)
+
     # -- episodic-return reduction (rl/callbacks.py:91-117 on_episode_end, summed over the batch) -------------------
     def reduce_episodes(self, clear=True, out=None):
         """float64 [3 + n_stats] on the env's GPU: sum of returns, sum of lengths, number of episodes, sum of final
@@ -779,12 +811,16 @@ class SubBatchedVecEnv:
         self.wait()
         return self._step_out
 
-    def _cat(self, parts, keys):
-        return SimpleNamespace(**{key: torch.cat([getattr(p, key) for p in parts]) for key in keys})
+    def _cat(self, parts, keys, **rest):
+        return SimpleNamespace(**{**rest, **{key: torch.cat([getattr(p, key) for p in parts]) for key in keys}})
 
     def get_state(self):
         return self._cat(self._each(lambda i, e: e.get_state()),
                          ("grids", "pos", "counters", "stats", "last_loss", "ep_return", "iteration", "changes", "n_step", "ep_len"))
+
+    def paths(self, cap=None, overlay=False):
+        return self._cat(self._each(lambda i, e: e.paths(cap=cap, overlay=overlay)),
+                         ("coords", "length") + (("overlay",) if overlay else ()), overlay=None)
 
     def reduce_episodes(self, clear=True):
         return torch.stack(self._each(lambda i, e: e.reduce_episodes(clear=clear))).sum(0)
