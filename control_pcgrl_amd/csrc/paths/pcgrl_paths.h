@@ -24,7 +24,8 @@
 //            row-major cell of their union (one flood) lies in it, a second flood cuts it out.
 //   zelda    the table is used twice: BFS from the player, trace from the key; BFS from the key, trace from the door.  A
 //            recorded BFS stops at the end of the trip in which it reaches its target.
-// The back-trace is a dependent chain of LDS reads, one step per path cell (at most 2 080 at 64 x 64, about 0.1 ms): every
+// The back-trace is a dependent chain of LDS reads, one step per path cell (at most n_cells for binary; the longest known at
+// 64 x 64 is a one-cell-wide spiral's 2 111, about 0.1 ms; zelda's two halves on a serpentine: 3 116 of 2 * n_cells): every
 // lane of the group walks it (the reads are broadcasts), the four neighbour reads of a step are issued together, lane i of
 // the group keeps the cell of step i mod LPE and the group stores LPE cells with one instruction; the (-1, -1) fill and the
 // overlay rows are written by all lanes in parallel.  Plain vector stores only.

@@ -2,6 +2,7 @@
 -> tests/golden/paths/{binary,zelda}_<H>x<W>.npz.
 
     python tools/gen_golden_paths.py            # everything (needs the reference tree; about a minute)
+    python tools/gen_golden_paths.py structured # only the structured set (below)
 
 binary: helper.calc_longest_path(map, locations, ["empty"], get_path=True), what BinaryProblem.get_stats keeps as path_coords.
 zelda:  ZeldaCtrlProblem(cfg).get_stats(map) with render_path = True, what it keeps as .path.
@@ -9,6 +10,14 @@ zelda:  ZeldaCtrlProblem(cfg).get_stats(map) with render_path = True, what it ke
 The files live in a sub-folder of tests/golden/ because other tests collect tests/golden/*.npz by pattern.  Layout: `grids`
 uint8 [n, H, W]; the ragged paths as `cells` int16 [total, 2] (row, col) with `offsets` int32 [n + 1]; binary: `L` int32 [n],
 the path-length statistic.  Every file starts with the hand-built maps (`n_hand` of them), random maps follow.
+
+A second, STRUCTURED set goes to tests/golden/paths/structured/ (a folder of its own, so that the paths/*.npz patterns do not
+see it): the same layout without n_hand, plus `names`, one family name per map.  Only hand-built maps, one shape per kernel
+form, an odd shape and the largest (STRUCTURED_SHAPES): the long paths, the tied components and routes and the one- and
+two-cell maps that random maps do not produce (structured_binary), and for zelda the key and the door at every distance
+1..7 from the player, both halves on a serpentine -- 3 116 cells at 64 x 64, with the player's cell walked twice -- and
+halves that are empty or share cells (structured_zelda).  The longest KNOWN binary path at 64 x 64 is the one-cell-wide
+spiral's, 2 111 cells (the serpentine has 2 080); the bound on a binary path is n_cells.
 
 The script fails unless the set tells the rules' tie-breaks apart (see check_worth): the fixtures are only worth replaying if
 another neighbour order, another choice among tied components or among tied end cells would fail them.
@@ -134,8 +143,135 @@ def check_worth(problem, shape, grids, paths):
     assert rev >= 20 and comp >= 5 and end >= 5, "the fixtures do not tell the tie-breaks apart"
 
 
+STRUCTURED_OUT = os.path.join(OUT, "structured")
+# one shape per kernel form (lanes per map / mask bits: 8/32, 16/32, 32/32, 64/32, 32/64, 64/64), an odd one, the largest
+STRUCTURED_SHAPES = [(8, 8), (5, 7), (16, 16), (20, 24), (40, 16), (12, 40), (40, 48), (64, 64)]
+
+
+def spiral(h, w):
+    """a one-cell-wide corridor wound inwards from (0, 0), one solid cell between its turns (64 x 64: 2 111 cells)"""
+    g = np.ones((h, w), np.uint8)
+    r, c, k = 0, 0, 0
+    g[0, 0] = 0
+    dirs = ((0, 1), (1, 0), (0, -1), (-1, 0))
+
+    def free(rr, cc):  # inside, solid, and touching no open cell but the one we come from
+        if not (0 <= rr < h and 0 <= cc < w) or g[rr, cc] == 0:
+            return False
+        return all((ar, ac) == (r, c) or not (0 <= ar < h and 0 <= ac < w) or g[ar, ac] == 1
+                   for ar, ac in ((rr - 1, cc), (rr + 1, cc), (rr, cc - 1), (rr, cc + 1)))
+
+    while True:
+        for turn in (0, 1):
+            dr, dc = dirs[(k + turn) % 4]
+            if free(r + dr, c + dc):
+                k, r, c = (k + turn) % 4, r + dr, c + dc
+                g[r, c] = 0
+                break
+        else:
+            return g
+
+
+def corridor(g):
+    """the cells of a one-corridor map in walking order from (0, 0)"""
+    d = pn.bfs(g == 0, (0, 0))
+    cells = np.argwhere(d >= 0)
+    return [tuple(int(v) for v in cells[i]) for i in np.argsort(d[d >= 0], kind="stable")]
+
+
+def structured_binary(shape):
+    """-> [(family name, map)]"""
+    h, w = shape
+    rr, cc = np.mgrid[0:h, 0:w]
+    solid = lambda: np.ones(shape, np.uint8)  # noqa: E731
+    comb = solid()  # row 0 and the even columns open
+    comb[0, :] = 0
+    comb[:, 0::2] = 0
+    rooms = np.zeros(shape, np.uint8)  # every fourth column solid: components that tie
+    rooms[:, 3::4] = 1
+    frame = solid()  # a cycle: routes that tie
+    frame[0, :] = frame[h - 1, :] = 0
+    frame[:, 0] = frame[:, w - 1] = 0
+    stairs = ((cc != rr) & (cc != rr + 1)).astype(np.uint8)
+    two, one = solid(), solid()
+    two[h - 1, w - 2:] = 0
+    one[h - 1, w - 1] = 0
+    return [("spiral", spiral(h, w)), ("comb", comb), ("checkerboard", ((rr + cc) % 2).astype(np.uint8)),
+            ("equal-rooms", rooms), ("open-frame", frame), ("staircase", stairs), ("two-cells-last-row", two),
+            ("one-cell-last-corner", one), ("serpentine", serpentine(h, w)),
+            ("serpentine-transposed", np.ascontiguousarray(serpentine(w, h).T))]
+
+
+def structured_zelda(shape):
+    """-> [(family name, map)]"""
+    h, w = shape
+    out = []
+    # the key and the door side by side in row 0, the nearer one d cells from the player: every residue of the recorded
+    # sweep's unrolling and its early stop; with the door in front the first half goes round it (open map) or does not exist
+    # (rows 1.. solid)
+    for ground in ("open", "row0"):
+        for first in ("key", "door"):
+            for d in range(1, 8):
+                if d + 1 >= w:
+                    continue
+                g = np.zeros(shape, np.uint8)
+                if ground == "row0":
+                    g[1:] = pn.SOLID
+                g[0, 0] = pn.PLAYER
+                g[0, d], g[0, d + 1] = (pn.KEY, pn.DOOR) if first == "key" else (pn.DOOR, pn.KEY)
+                out.append((f"{ground}-{first}-first-d{d}", g))
+    for name, base in (("serpentine", serpentine(h, w)), ("serpentine-transposed", np.ascontiguousarray(serpentine(w, h).T))):
+        way = corridor(base)
+        g = base.copy()  # no door: no path
+        g[way[0]], g[way[-1]] = pn.PLAYER, pn.KEY
+        out.append((f"{name}-no-door", g))
+        g = g.copy()  # the door in front of the player: only the half from the door to the key
+        g[way[1]] = pn.DOOR
+        out.append((f"{name}-door-second-cell", g))
+        g = base.copy()  # both halves, the second one through the player's cell
+        g[way[0]], g[way[len(way) // 2]], g[way[-1]] = pn.KEY, pn.PLAYER, pn.DOOR
+        out.append((f"{name}-player-middle", g))
+        g = g.copy()
+        for i, cell in enumerate(way[2:-2:5]):
+            if g[cell] == pn.EMPTY:
+                g[cell] = 5 + i % 3
+        out.append((f"{name}-player-middle-enemies", g))
+    g = np.zeros(shape, np.uint8)  # the halves share cells
+    g[0, 0], g[0, 1], g[h - 1, w - 1] = pn.PLAYER, pn.DOOR, pn.KEY
+    out.append(("open-key-far-door-near", g))
+    return out
+
+
+def structured():
+    os.makedirs(STRUCTURED_OUT, exist_ok=True)
+    total = 0
+    for problem, family in (("binary", structured_binary), ("zelda", structured_zelda)):
+        for shape in STRUCTURED_SHAPES:
+            named = family(shape)
+            grids = np.array([g for _, g in named], np.uint8)
+            paths, lens = reference_paths(problem, shape, grids)
+            for g, p, length in zip(grids, paths, lens):  # the numpy rules reproduce every recorded path
+                mine = pn.path_of(problem, g)
+                assert len(mine) == len(p) and all(tuple(a) == tuple(b) for a, b in zip(mine, p)), (problem, shape, g, p, mine)
+                assert problem != "binary" or len(p) == (length + 1 if length else 0)
+            out = dict(grids=grids, offsets=np.cumsum([0] + [len(p) for p in paths]).astype(np.int32),
+                       cells=np.concatenate(paths).astype(np.int16), names=np.array([name for name, _ in named]))
+            if problem == "binary":
+                out["L"] = np.array(lens, np.int32)
+            path = os.path.join(STRUCTURED_OUT, f"{problem}_{shape[0]}x{shape[1]}.npz")
+            np.savez_compressed(path, **out)
+            total += os.path.getsize(path)
+            print(f"{os.path.relpath(path, ROOT)}: {len(grids)} maps, longest path {max(len(p) for p in paths)}, "
+                  f"{os.path.getsize(path)} bytes")
+            assert os.path.getsize(path) <= 16 * 1024
+    print("structured total", total, "bytes")
+    assert total <= 100 * 1024
+
+
 def main():
     assert ref_env.available(), "reference tree not present"
+    if sys.argv[1:] == ["structured"]:
+        return structured()
     os.makedirs(OUT, exist_ok=True)
     total = 0
     for problem in ("binary", "zelda"):
@@ -160,6 +296,7 @@ def main():
                   f"{max(len(p) for p in paths)}, {os.path.getsize(path)} bytes")
     print("total", total, "bytes")
     assert total < 300 * 1024
+    structured()
 
 
 if __name__ == "__main__":
