@@ -24,9 +24,11 @@
 #include "reps3d/pcgrl_reps3d.h"  // the 3-D maze under turtle / wide
 #include "async3d/pcgrl_async3d.h"  // the 3-D maze (narrow) under a solver budget
 #include "paths/pcgrl_paths.h"      // solution paths of binary / zelda maps
+#include "solutions/pcgrl_solutions.h"  // sokoban solutions (the move list behind sol-length)
 #include "../../include/pcgrl_amd_codes.h"
 #include "../../include/pcgrl_amd_async3d.h"
 #include "../../include/pcgrl_amd_paths.h"
+#include "../../include/pcgrl_amd_solutions.h"
 
 using namespace pcgrl;
 
@@ -1795,6 +1797,48 @@ int pcgrl_paths(pcgrl_handle h, int32_t cap, int16_t *d_path, int32_t *d_len, ui
 int pcgrl_paths_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t cap, int16_t *d_path, int32_t *d_len,
                           uint8_t *d_overlay, void *stream) {
   return paths_launch(h, "pcgrl_paths_for_grids", false, n, d_grids, cap, d_path, d_len, d_overlay, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- sokoban solutions
+// include/pcgrl_amd_solutions.h; kernel in solutions/pcgrl_solutions.h
+int32_t pcgrl_solution_capacity(pcgrl_handle h) {
+  if (!h) return -1;
+  return h->p.cfg.problem == PCGRL_PROB_SOKOBAN ? h->p.cfg.solver_power : 0;  // (no solver, no solution)
+}
+
+// n maps -- the engine's own (d_grids == nullptr, own) or the caller's -- through the solution kernel
+static int solutions_launch(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t cap, int8_t *d_moves,
+                            int32_t *d_len, int32_t *d_dist_win, void *stream) {
+  if (!h || cap < 1 || n < 0 || (n > 0 && (!d_moves || !d_len || (!own && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (h->p.cfg.problem != PCGRL_PROB_SOKOBAN || !h->p.soko)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": only sokoban has a solver and a solution (paths: pcgrl_amd_paths.h)");
+  if (n == 0) return PCGRL_OK;
+  ON_DEVICE(h->device);
+  Params p = h->p;
+  // one search per workgroup, each on a slot of the synchronous pool -- also under a solver budget: the per-env workspaces of
+  // asynchronous stepping and their park records are not touched.  A batch much larger than the pool gets a larger pool the
+  // first time, as in pcgrl_stats_for_grids_h (never while `stream` is being captured: searches then wait for a slot)
+  soko_pool_for(h, p, std::min(256, sokoban_slots_for(n)), (hipStream_t)stream);
+  p.n_envs = n;  // the kernel touches no per-env engine state but the tile planes
+  p.init_grids = d_grids;
+  SolArgs a;
+  a.moves = d_moves;
+  a.len = d_len;
+  a.dist_win = d_dist_win;
+  a.cap = cap;
+  a.from_grids = own ? 0 : 1;
+  HIPCHK(launch_solutions(p, h->lpe, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_solutions(pcgrl_handle h, int32_t cap, int8_t *d_moves, int32_t *d_len, int32_t *d_dist_win, void *stream) {
+  return solutions_launch(h, "pcgrl_solutions", true, h ? h->p.n_envs : 0, nullptr, cap, d_moves, d_len, d_dist_win, stream);
+}
+
+int pcgrl_solutions_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t cap, int8_t *d_moves, int32_t *d_len,
+                              int32_t *d_dist_win, void *stream) {
+  return solutions_launch(h, "pcgrl_solutions_for_grids", false, n, d_grids, cap, d_moves, d_len, d_dist_win, stream);
 }
 
 }  // extern "C"

@@ -175,6 +175,18 @@ class PcgrlGymEnv:
 
     path = path_coords
 
+    @property
+    def solution(self):
+        """The solution of the current sokoban map as the reference's get_stats(map)["solution"] (sokoban_prob.py:178): a list
+        of {"x": dx, "y": dy} moves ([] when no stage of the solver won); None when the statistics have no such key (the
+        solver's precondition does not hold)."""
+        s = self._vec.solutions()
+        n = int(s.length[0])
+        if n < 0:
+            return None
+        directions = ({"x": -1, "y": 0}, {"x": 1, "y": 0}, {"x": 0, "y": -1}, {"x": 0, "y": 1})  # engine.py:3
+        return [dict(directions[m]) for m in s.moves[0, :n].cpu().tolist()]
+
     def close(self):
         self._vec.close()
 

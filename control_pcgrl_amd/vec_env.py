@@ -659,6 +659,42 @@ class VecPcgrlEnv:
         g = torch.as_tensor(grids, device=self.device).to(torch.uint8).contiguous()
         return self._paths(g.numel() // self.n_cells, g, cap, overlay)
 
+    # -- sokoban solutions (include/pcgrl_amd_solutions.h) -----------------------------------------------------------
+    def _solutions(self, n, grids, cap, dist_win):
+        if cap is None:  # (a problem without a solver reports 0: the call below is what refuses it)
+            cap = max(1, int(self._L.pcgrl_solution_capacity(self._h)))
+        cap, dev = int(cap), self.device
+        out = SimpleNamespace(moves=torch.empty((n, cap), dtype=torch.int8, device=dev),
+                              length=torch.empty(n, dtype=torch.int32, device=dev),
+                              dist_win=torch.empty(n, dtype=torch.int32, device=dev) if dist_win else None)
+        dw = out.dist_win.data_ptr() if dist_win else None
+        if grids is None:
+            _lib.check(self._L.pcgrl_solutions(self._h, cap, out.moves.data_ptr(), out.length.data_ptr(), dw, self._stream()),
+                       "pcgrl_solutions")
+        else:
+            _lib.check(self._L.pcgrl_solutions_for_grids(self._h, n, grids.data_ptr(), cap, out.moves.data_ptr(),
+                                                         out.length.data_ptr(), dw, self._stream()),
+                       "pcgrl_solutions_for_grids")
+        return out
+
+    def solutions(self, cap=None, dist_win=False):
+        """The solution of every env's current sokoban map: the move list the reference's get_stats leaves in
+        stats["solution"] (sokoban_prob.py:178), whose length is `sol-length`:
+          moves     int8 [N, cap]   the first min(length, cap) moves in playing order as indices into the reference's
+                                    `directions` (engine.py:3: 0 = x-1, 1 = x+1, 2 = y-1, 3 = y+1), then -1
+          length    int32 [N]       the full length; 0: no stage of the solver won; -1: the solver's precondition (one
+                                    player, crates == targets > 0, one region) does not hold
+          dist_win  int32 [N]       `dist-win` of the statistics (dist_win=True), else None
+        cap=None: solver_power, the longest solution there can be.  A function of the map and solver_power alone (stale
+        statistics and a solver budget do not matter); one launch on the current stream, no host sync.  Other problems:
+        NotImplementedError."""
+        return self._solutions(self.num_envs, None, cap, dist_win)
+
+    def solutions_for_grids(self, grids, cap=None, dist_win=False):
+        """solutions() of caller maps (any number of them, uint8 tile ids of this env's map shape)."""
+        g = torch.as_tensor(grids, device=self.device).to(torch.uint8).contiguous()
+        return self._solutions(g.numel() // self.n_cells, g, cap, dist_win)
+
     # -- episodic-return reduction (rl/callbacks.py:91-117 on_episode_end, summed over the batch) -------------------
     def reduce_episodes(self, clear=True, out=None):
         """float64 [3 + n_stats] on the env's GPU: sum of returns, sum of lengths, number of episodes, sum of final
@@ -821,6 +857,10 @@ class SubBatchedVecEnv:
     def paths(self, cap=None, overlay=False):
         return self._cat(self._each(lambda i, e: e.paths(cap=cap, overlay=overlay)),
                          ("coords", "length") + (("overlay",) if overlay else ()), overlay=None)
+
+    def solutions(self, cap=None, dist_win=False):
+        return self._cat(self._each(lambda i, e: e.solutions(cap=cap, dist_win=dist_win)),
+                         ("moves", "length") + (("dist_win",) if dist_win else ()), dist_win=None)
 
     def reduce_episodes(self, clear=True):
         return torch.stack(self._each(lambda i, e: e.reduce_episodes(clear=clear))).sum(0)

@@ -14,7 +14,8 @@
  *             153-165): key -> player, then door -> key, without the cells of the player, the
  *             key and the door; empty unless there is exactly one of each.  A half whose
  *             target is walled in is empty, the other half stays.
- *   sokoban   PCGRL_EUNSUPPORTED: its "solution" is an action list out of a transient search, not a path.
+ *   sokoban   PCGRL_EUNSUPPORTED: its "solution" is an action list out of a transient search, not a path
+ *             (pcgrl_amd_solutions.h hands that list out).
  *   3-D maze  PCGRL_EUNSUPPORTED: the path is already the overlay channel of the observation (pcgrl_observe).
  *
  * The path is a function of the map alone: the state of the statistics (stale after pcgrl_update) and the representation
