@@ -4,6 +4,7 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   make_env(cfg)            single-env adapter with the reference's reset()/step() tuple shapes
   make_vec_env(cfg, n)     batched engine: torch tensors in/out, one HIP launch per step for all envs
   VecPcgrlEnv              the batched env class
+  MultiAgentVecEnv         cfg.multiagent.n_agents != 0: A turtle agents on one map, a round per launch (binary, zelda)
   PcgrlVectorEnv           the same batch behind ray.rllib's VectorEnv call shape (vector_step / reset_at ...)
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
@@ -14,6 +15,7 @@ from .problems import PROBLEMS, REPRESENTATIONS, ProblemSpec, problem_spec  # no
 from .vec_env import OBS_FORMATS, SubBatchedVecEnv, VecPcgrlEnv, codes_to_onehot, flatten_wide_action, make_vec_env  # noqa: F401
 from .envs import make_env, PcgrlGymEnv  # noqa: F401
 from .rllib_env import PcgrlVectorEnv  # noqa: F401
+from .multiagent import MultiAgentGymEnv, MultiAgentVecEnv  # noqa: F401
 from .dist import EpisodeStatsReducer, shard_env_range  # noqa: F401
 
-__version__ = "0.6.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number
+__version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

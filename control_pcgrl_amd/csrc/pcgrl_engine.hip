@@ -25,10 +25,12 @@
 #include "async3d/pcgrl_async3d.h"  // the 3-D maze (narrow) under a solver budget
 #include "paths/pcgrl_paths.h"      // solution paths of binary / zelda maps
 #include "solutions/pcgrl_solutions.h"  // sokoban solutions (the move list behind sol-length)
+#include "multiagent/pcgrl_multiagent.h"  // multi-agent turtle stepping (binary, zelda)
 #include "../../include/pcgrl_amd_codes.h"
 #include "../../include/pcgrl_amd_async3d.h"
 #include "../../include/pcgrl_amd_paths.h"
 #include "../../include/pcgrl_amd_solutions.h"
+#include "../../include/pcgrl_amd_multiagent.h"
 
 using namespace pcgrl;
 
@@ -85,6 +87,12 @@ struct pcgrl_engine {
   int32_t obs_shape[4] = {0, 0, 0, 0};
   RedScratch *red = nullptr;  // pcgrl_reduce_episodes block partials
   SampleState *sample = nullptr;  // pcgrl_sample_actions: draw counter + ticket
+  // multi-agent turtle stepping (pcgrl_ma_attach): the side arrays and the shape of one agent's observation
+  bool ma_on = false;
+  MaArgs ma = {};
+  size_t ma_lds = 0;
+  int64_t ma_obs_bytes = 0;
+  int32_t ma_obs_shape[3] = {0, 0, 0};
   std::vector<void *> allocs;
   // the persistent per-env arrays (pointer, bytes per env): what pcgrl_export_state / pcgrl_import_state carry
   std::vector<std::pair<void *, size_t>> state_arrays;
@@ -608,7 +616,7 @@ static void choose_spread(pcgrl_engine *h, Params &p) {
 extern "C" {
 
 const char *pcgrl_last_error(void) { return g_err.c_str(); }
-const char *pcgrl_version(void) { return "pcgrl_amd 0.6.0 (gfx950)"; }
+const char *pcgrl_version(void) { return "pcgrl_amd 0.7.0 (gfx950)"; }
 
 int pcgrl_create(const pcgrl_config *cfg, int32_t n_envs, int32_t device, pcgrl_handle *out) {
   if (!cfg || !out || n_envs < 1) return fail(PCGRL_EINVAL, "pcgrl_create: bad arguments");
@@ -837,6 +845,7 @@ int pcgrl_seed(pcgrl_handle h, const uint64_t *seeds) {
   HIPCHK(hipMemcpy(h->p.rng, r.data(), r.size() * sizeof(RngState), hipMemcpyHostToDevice));
   // seeding a numpy bit generator drops the spare 32 bits of its last draw
   if (h->p.xstate) HIPCHK(hipMemset(h->p.xstate, 0, (size_t)h->p.n_envs * 4 * sizeof(uint32_t)));
+  if (h->ma_on) HIPCHK(hipMemset2D(h->ma.side + 1, 4 * sizeof(uint32_t), 0, 2 * sizeof(uint32_t), (size_t)h->p.n_envs));
   return PCGRL_OK;
 }
 
@@ -850,8 +859,15 @@ static bool async_capable(const pcgrl_engine *h) {
   return h->p.soko != nullptr || (h->p.cfg.problem == PCGRL_PROB_MC3DMAZE && h->p.cfg.representation == PCGRL_REP_NARROW);
 }
 
+// the single-agent stepping entry points on an engine that pcgrl_ma_attach has made a multi-agent one
+#define NOT_ATTACHED(h, what)                                                                                             \
+  if ((h)->ma_on)                                                                                                         \
+  return fail(PCGRL_EINVAL, std::string(what) + ": the engine steps several agents (pcgrl_ma_attach): use the pcgrl_ma_* entry " \
+                                                "points of pcgrl_amd_multiagent.h")
+
 int pcgrl_reset(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_init_grids, const int32_t *d_init_pos, void *stream) {
   if (!h) return fail(PCGRL_EINVAL, "pcgrl_reset: null handle");
+  NOT_ATTACHED(h, "pcgrl_reset");
   ON_DEVICE(h->device);
   Params p = h->p;
   soko_pool_lazy(h, p, (hipStream_t)stream);
@@ -873,6 +889,7 @@ int pcgrl_step(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, uin
                int32_t *d_stats, void *stream) {
   if (!h || !d_actions) return fail(PCGRL_EINVAL, "pcgrl_step: bad arguments");
   NOT_WITH_BUDGET(h, "pcgrl_step");
+  NOT_ATTACHED(h, "pcgrl_step");
   ON_DEVICE(h->device);
   Params p = h->p;
   p.no_fast = h->maybe_stale ? 1 : 0;
@@ -905,6 +922,7 @@ int pcgrl_step_ex(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, 
                   double *d_reward64, uint8_t *d_done, int32_t *d_stats, float *d_ctrl_obs, void *stream) {
   if (!h || !d_actions) return fail(PCGRL_EINVAL, "pcgrl_step_ex: bad arguments");
   NOT_WITH_BUDGET(h, "pcgrl_step_ex");
+  NOT_ATTACHED(h, "pcgrl_step_ex");
   ON_DEVICE(h->device);
   if (d_ctrl_obs && h->p.cfg.n_ctrl == 0) return fail(PCGRL_EINVAL, "pcgrl_step_ex: d_ctrl_obs needs cfg.n_ctrl > 0");
   Params p = h->p;
@@ -954,6 +972,7 @@ int pcgrl_rollout_ex(pcgrl_handle h, const int32_t *d_actions, int32_t n_steps, 
                      void *stream) {
   if (!h || !d_actions || n_steps < 1) return fail(PCGRL_EINVAL, "pcgrl_rollout: bad arguments");
   NOT_WITH_BUDGET(h, "pcgrl_rollout");
+  NOT_ATTACHED(h, "pcgrl_rollout");
   if (d_ctrl_obs && h->p.cfg.n_ctrl == 0) return fail(PCGRL_EINVAL, "pcgrl_rollout_ex: d_ctrl_obs needs cfg.n_ctrl > 0");
   if (rollout_as_steps(h)) {
     const size_t N = (size_t)h->p.n_envs;
@@ -1061,6 +1080,7 @@ int pcgrl_rollout(pcgrl_handle h, const int32_t *d_actions, int32_t n_steps, int
 int pcgrl_update(pcgrl_handle h, const int32_t *d_actions, uint8_t *d_obs, void *stream) {
   if (!h || !d_actions) return fail(PCGRL_EINVAL, "pcgrl_update: bad arguments");
   NOT_WITH_BUDGET(h, "pcgrl_update");
+  NOT_ATTACHED(h, "pcgrl_update");
   ON_DEVICE(h->device);
   Params p = h->p;
   p.actions = d_actions;
@@ -1131,6 +1151,7 @@ int pcgrl_ctrl_observe(pcgrl_handle h, float *d_ctrl_obs, void *stream) {
 
 int pcgrl_observe(pcgrl_handle h, uint8_t *d_obs, void *stream) {
   if (!h || !d_obs) return fail(PCGRL_EINVAL, "pcgrl_observe: bad arguments");
+  NOT_ATTACHED(h, "pcgrl_observe");
   ON_DEVICE(h->device);
   Params p = h->p;
   p.obs = d_obs;
@@ -1499,6 +1520,7 @@ int pcgrl_sample_actions(pcgrl_handle h, int32_t *d_actions, uint64_t seed, void
 
 int pcgrl_set_solver_budget(pcgrl_handle h, int32_t budget) {
   if (!h || budget < 0) return fail(PCGRL_EINVAL, "pcgrl_set_solver_budget: bad arguments");
+  NOT_ATTACHED(h, "pcgrl_set_solver_budget");
   const bool maze3d = h->p.cfg.problem == PCGRL_PROB_MC3DMAZE;
   if (maze3d && h->p.cfg.representation != PCGRL_REP_NARROW)
     return fail(PCGRL_EUNSUPPORTED, "pcgrl_set_solver_budget: minecraft_3D_maze steps asynchronously under the narrow representation only "
@@ -1839,6 +1861,149 @@ int pcgrl_solutions(pcgrl_handle h, int32_t cap, int8_t *d_moves, int32_t *d_len
 int pcgrl_solutions_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t cap, int8_t *d_moves, int32_t *d_len,
                               int32_t *d_dist_win, void *stream) {
   return solutions_launch(h, "pcgrl_solutions_for_grids", false, n, d_grids, cap, d_moves, d_len, d_dist_win, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- multi-agent turtle stepping
+// include/pcgrl_amd_multiagent.h; kernels in multiagent/pcgrl_multiagent.h
+int pcgrl_ma_attach(pcgrl_handle h, int32_t n_agents, int32_t show_agents) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_ma_attach: null handle");
+  if (h->ma_on) return fail(PCGRL_EINVAL, "pcgrl_ma_attach: the engine is attached already");
+  if (n_agents < 1 || n_agents > PCGRL_MA_MAX_AGENTS)
+    return fail(PCGRL_EINVAL, "pcgrl_ma_attach: n_agents must be in [1, " + std::to_string(PCGRL_MA_MAX_AGENTS) + "]");
+  const pcgrl_config &c = h->p.cfg;
+  if (c.representation != PCGRL_REP_TURTLE)
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: the turtle representation only (the reference's multi-agent narrow raises "
+                                    "'Busted for now' and its multi-agent wide a TypeError)");
+  if (c.problem != PCGRL_PROB_BINARY && c.problem != PCGRL_PROB_ZELDA)
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: binary and zelda only (sokoban and the 3-D maze need the helper-wave and "
+                                    "workspace machinery of their searches, which the multi-agent kernels do not carry)");
+  if (c.static_tiles) return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: not with static tiles");
+  if (c.act_window[0] != 0 || c.act_window[1] != 0) return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: not with an action patch");
+  if (c.n_ctrl > 0) return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: not with control metrics");
+  if (h->sk_budget > 0) return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: not with a solver budget");
+  if (show_agents && n_agents == 1)
+    return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: show_agents needs more than one agent (the reference's "
+                                    "ShowAgentRepresentation raises with one)");
+  if (h->maybe_stale) return fail(PCGRL_EINVAL, "pcgrl_ma_attach: pcgrl_update has left statistics stale (pcgrl_refresh_stats first)");
+  const int OH = c.obs_window[0], OW = c.obs_window[1], C = h->p.n_tiles + 1 + (show_agents ? 1 : 0);
+  const int chunks = (OW * C + 15) / 16;
+  const size_t lds = show_agents ? (size_t)(chunks * 16 + 16) * 65 : h->lds_bytes;
+  if (lds > 160 * 1024) return fail(PCGRL_EUNSUPPORTED, "pcgrl_ma_attach: the observation rows with the occupancy channel exceed the LDS");
+  ON_DEVICE(h->device);
+  const size_t N = (size_t)h->p.n_envs, A = (size_t)n_agents;
+  MaArgs a = {};
+  a.n_agents = n_agents;
+  a.show_agents = show_agents ? 1 : 0;
+  a.obs_chunks = chunks;
+  void *ptr[3] = {nullptr, nullptr, nullptr};
+  const size_t bytes[3] = {N * A * 2 * sizeof(int32_t), N * 4 * sizeof(uint32_t), N * A * PCGRL_MAX_STATS * sizeof(int32_t)};
+  for (int i = 0; i < 3; i++) {
+    hipError_t err = hipMalloc(&ptr[i], bytes[i]);
+    if (err == hipSuccess) {
+      h->allocs.push_back(ptr[i]);  // (freed with the engine, also when a later allocation fails)
+      err = hipMemset(ptr[i], 0, bytes[i]);
+    }
+    if (err != hipSuccess) return fail(PCGRL_EHIP, std::string("pcgrl_ma_attach: ") + hipGetErrorString(err));
+  }
+  a.pos = (int32_t *)ptr[0];
+  a.side = (uint32_t *)ptr[1];
+  a.last_stats = (int32_t *)ptr[2];
+  h->ma = a;
+  h->ma_lds = lds;
+  h->ma_obs_bytes = (int64_t)OH * OW * C;
+  h->ma_obs_shape[0] = OH;
+  h->ma_obs_shape[1] = OW;
+  h->ma_obs_shape[2] = C;
+  h->ma_on = true;
+  return PCGRL_OK;
+}
+
+int32_t pcgrl_ma_attached(pcgrl_handle h) { return h ? (h->ma_on ? 1 : 0) : -1; }
+
+#define MA_ATTACHED(h, what)                                                                        \
+  if (!(h)) return fail(PCGRL_EINVAL, std::string(what) + ": null handle");                         \
+  if (!(h)->ma_on) return fail(PCGRL_EINVAL, std::string(what) + ": the engine is not attached (pcgrl_ma_attach)")
+
+int pcgrl_ma_obs_shape(pcgrl_handle h, int32_t shape_out[4], int32_t *ndim_out) {
+  MA_ATTACHED(h, "pcgrl_ma_obs_shape");
+  if (!shape_out || !ndim_out) return fail(PCGRL_EINVAL, "pcgrl_ma_obs_shape: bad arguments");
+  for (int i = 0; i < 4; i++) shape_out[i] = i < 3 ? h->ma_obs_shape[i] : 0;
+  *ndim_out = 3;
+  return PCGRL_OK;
+}
+
+int pcgrl_ma_observe(pcgrl_handle h, uint8_t *d_obs, void *stream) {
+  MA_ATTACHED(h, "pcgrl_ma_observe");
+  if (!d_obs) return fail(PCGRL_EINVAL, "pcgrl_ma_observe: bad arguments");
+  ON_DEVICE(h->device);
+  Params p = h->p;
+  p.obs = d_obs;
+  HIPCHK(launch_ma(MA_OBSERVE, p, h->lpe, h->ma, h->ma_lds, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_ma_reset(pcgrl_handle h, const uint8_t *d_mask, const uint8_t *d_init_grids, const int32_t *d_init_pos, uint8_t *d_obs,
+                   void *stream) {
+  MA_ATTACHED(h, "pcgrl_ma_reset");
+  if ((d_init_grids == nullptr) != (d_init_pos == nullptr))
+    return fail(PCGRL_EINVAL, "pcgrl_ma_reset: injected maps and injected positions come together");
+  ON_DEVICE(h->device);
+  Params p = h->p;
+  p.mask = d_mask;
+  p.init_grids = d_init_grids;
+  MaArgs a = h->ma;
+  a.init_pos = d_init_pos;
+  HIPCHK(launch_ma(MA_RESET, p, h->lpe, a, 0, (hipStream_t)stream));
+  if (d_obs) {
+    p.obs = d_obs;
+    HIPCHK(launch_ma(MA_OBSERVE, p, h->lpe, h->ma, h->ma_lds, (hipStream_t)stream));
+  }
+  return PCGRL_OK;
+}
+
+int pcgrl_ma_step(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, uint8_t *d_obs, float *d_reward, uint8_t *d_done,
+                  int32_t *d_stats, uint8_t *d_done_all, void *stream) {
+  MA_ATTACHED(h, "pcgrl_ma_step");
+  if (!d_actions) return fail(PCGRL_EINVAL, "pcgrl_ma_step: bad arguments");
+  ON_DEVICE(h->device);
+  Params p = h->p;
+  p.actions = d_actions;
+  p.auto_reset = auto_reset;
+  p.obs = d_obs;
+  p.reward = d_reward;
+  p.done = d_done;
+  p.stats_out = d_stats;
+  MaArgs a = h->ma;
+  a.done_all = d_done_all;
+  HIPCHK(launch_ma(MA_STEP, p, h->lpe, a, h->ma_lds, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_ma_get_state(pcgrl_handle h, int32_t *d_pos, uint32_t *d_side, int32_t *d_last_stats, void *stream) {
+  MA_ATTACHED(h, "pcgrl_ma_get_state");
+  ON_DEVICE(h->device);
+  const size_t N = (size_t)h->p.n_envs, A = (size_t)h->ma.n_agents;
+  hipStream_t s = (hipStream_t)stream;
+  if (d_pos) HIPCHK(hipMemcpyAsync(d_pos, h->ma.pos, N * A * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (d_side) HIPCHK(hipMemcpyAsync(d_side, h->ma.side, N * 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  if (d_last_stats)
+    HIPCHK(hipMemcpyAsync(d_last_stats, h->ma.last_stats, N * A * PCGRL_MAX_STATS * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return PCGRL_OK;
+}
+
+int pcgrl_ma_set_state(pcgrl_handle h, const uint8_t *d_mask, const int32_t *d_pos, const uint32_t *d_side,
+                       const int32_t *d_last_stats, void *stream) {
+  MA_ATTACHED(h, "pcgrl_ma_set_state");
+  if (!d_pos && !d_side && !d_last_stats) return PCGRL_OK;
+  ON_DEVICE(h->device);
+  Params p = h->p;
+  p.mask = d_mask;
+  MaArgs a = h->ma;
+  a.init_pos = d_pos;
+  a.in_side = d_side;
+  a.in_stats = d_last_stats;
+  HIPCHK(launch_ma(MA_SET_STATE, p, h->lpe, a, 0, (hipStream_t)stream));
+  return PCGRL_OK;
 }
 
 }  // extern "C"

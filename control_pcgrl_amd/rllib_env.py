@@ -36,7 +36,7 @@ import torch
 
 from . import _lib
 from .envs import Discrete, MultiDiscrete, _observation_space
-from .vec_env import VecPcgrlEnv, make_vec_env
+from .vec_env import VecPcgrlEnv, _cfg_get, make_vec_env
 
 try:  # pragma: no cover - ray is not in the build image
     from ray.rllib.env.vector_env import VectorEnv as _Base
@@ -124,6 +124,9 @@ class PcgrlVectorEnv(_Base):
 
     def __init__(self, cfg=None, num_envs=1, device="cuda:0", seeds=None, vec: VecPcgrlEnv = None, obs_dtype=np.float32,
                  direct_host_outputs=None):
+        if vec is None and _cfg_get(cfg, "multiagent.n_agents", 0):
+            raise NotImplementedError("PcgrlVectorEnv with multiagent.n_agents: RLlib's VectorEnv has one agent per sub-env; use "
+                                      "multiagent.MultiAgentVecEnv (batched) or make_env(cfg) (the reference's dict call shape)")
         self.vec = vec if vec is not None else make_vec_env(cfg, num_envs, device=device, seeds=seeds, auto_reset=False)
         v = self.vec
         assert not v.auto_reset, "PcgrlVectorEnv drives resets itself (RLlib calls reset_at)"

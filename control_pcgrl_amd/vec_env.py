@@ -938,15 +938,20 @@ class SubBatchedVecEnv:
 def make_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, sub_batches=1):
     """Batched counterpart of control_pcgrl/rl/envs.py:make_env(cfg).  `cfg` is the reference's Config-like
     object (attributes or dict keys): task.problem, task.map_shape, task.obs_window, task.weights,
-    representation, max_board_scans, change_percentage; obs_format ("onehot" default, or "codes": VecPcgrlEnv)."""
+    representation, max_board_scans, change_percentage; obs_format ("onehot" default, or "codes": VecPcgrlEnv).
+    cfg.multiagent.n_agents != 0 (with or without cfg.show_agents): a multiagent.MultiAgentVecEnv."""
     unsupported = {
         "n_aux_tiles": _cfg_get(cfg, "n_aux_tiles", 0) or None,
-        "show_agents": _cfg_get(cfg, "show_agents", False) or None,
-        "multiagent.n_agents": _cfg_get(cfg, "multiagent.n_agents", 0) or None,
     }
     bad = {k: v for k, v in unsupported.items() if v not in (None, 0, False)}
     if bad:
         raise NotImplementedError(f"outside the accelerated hot path (SURVEY.md section 8f 'next'): {bad}")
+    if _cfg_get(cfg, "multiagent.n_agents", 0):
+        from .multiagent import make_multiagent_vec_env
+        return make_multiagent_vec_env(cfg, num_envs, device=device, seeds=seeds, auto_reset=auto_reset, sub_batches=sub_batches)
+    if _cfg_get(cfg, "show_agents", False):
+        raise NotImplementedError("show_agents needs multiagent.n_agents >= 2 (the reference's ShowAgentRepresentation has no "
+                                  "positions to show without the multi-agent wrapper)")
     if int(sub_batches) > 1 and _cfg_get(cfg, "controls"):
         raise NotImplementedError("sub_batches > 1 with cfg.controls: SubBatchedVecEnv.step() has no float64 rewards / control "
                                   "observation of the whole batch (use sub_batches=1, or step_async per sub-batch)")
