@@ -13,10 +13,11 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "pcgrl_k_sokoban32_64.hip", "pcgrl_k_sokoban64_32.hip", "pcgrl_k_sokoban64_64.hip", "pcgrl_k_3d.hip",
          "codes/pcgrl_codes.hip", "reps3d/pcgrl_k_3d_turtle.hip", "reps3d/pcgrl_k_3d_wide.hip",
          "async3d/pcgrl_k_3d_async.hip", "paths/pcgrl_k_paths_binary.hip", "paths/pcgrl_k_paths_zelda.hip",
-         "solutions/pcgrl_k_solutions.hip", "multiagent/pcgrl_k_ma_binary.hip", "multiagent/pcgrl_k_ma_zelda.hip"]
+         "solutions/pcgrl_k_solutions.hip", "multiagent/pcgrl_k_ma_binary.hip", "multiagent/pcgrl_k_ma_zelda.hip",
+         "measures/pcgrl_k_measures.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
-           "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h"]
+           "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -24,6 +25,7 @@ ASYNC3D_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_asyn
 PATHS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_paths.h")
 SOLUTIONS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_solutions.h")
 MULTIAGENT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_multiagent.h")
+MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_measures.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -146,6 +148,16 @@ MULTIAGENT_SYMBOLS = {
     "pcgrl_ma_set_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
 }
 
+# include/pcgrl_amd_measures.h: level measures and pairwise Hamming diversity of 2-D maps
+MEASURES_SYMBOLS = {
+    "pcgrl_measures_tiles": (C.c_int32, [C.c_void_p]),
+    "pcgrl_measures": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
+    "pcgrl_measures_for_grids": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+    "pcgrl_diversity_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "pcgrl_diversity": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+    "pcgrl_diversity_for_grids": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -153,7 +165,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     `out` / `defines`: development builds (tools/phase_timing.py, tools/wave_trace.py)."""
     out = out or LIB_PATH
     srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER, ASYNC3D_HEADER, PATHS_HEADER,
-                                                       SOLUTIONS_HEADER, MULTIAGENT_HEADER]
+                                                       SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -163,7 +175,8 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     os.makedirs(objdir, exist_ok=True)
     hdr_time = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     hdr_time = max(hdr_time, os.path.getmtime(HEADER), os.path.getmtime(CODES_HEADER), os.path.getmtime(ASYNC3D_HEADER),
-                   os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER))
+                   os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER),
+                   os.path.getmtime(MEASURES_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -209,7 +222,7 @@ def lib():
         L = C.CDLL(override or LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(CODES_SYMBOLS.items()) + list(ASYNC3D_SYMBOLS.items())
                                   + list(PATHS_SYMBOLS.items()) + list(SOLUTIONS_SYMBOLS.items())
-                                  + list(MULTIAGENT_SYMBOLS.items())):
+                                  + list(MULTIAGENT_SYMBOLS.items()) + list(MEASURES_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -26,11 +26,13 @@
 #include "paths/pcgrl_paths.h"      // solution paths of binary / zelda maps
 #include "solutions/pcgrl_solutions.h"  // sokoban solutions (the move list behind sol-length)
 #include "multiagent/pcgrl_multiagent.h"  // multi-agent turtle stepping (binary, zelda)
+#include "measures/pcgrl_measures.h"  // level measures and pairwise Hamming diversity of 2-D maps
 #include "../../include/pcgrl_amd_codes.h"
 #include "../../include/pcgrl_amd_async3d.h"
 #include "../../include/pcgrl_amd_paths.h"
 #include "../../include/pcgrl_amd_solutions.h"
 #include "../../include/pcgrl_amd_multiagent.h"
+#include "../../include/pcgrl_amd_measures.h"
 
 using namespace pcgrl;
 
@@ -1861,6 +1863,112 @@ int pcgrl_solutions(pcgrl_handle h, int32_t cap, int8_t *d_moves, int32_t *d_len
 int pcgrl_solutions_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t cap, int8_t *d_moves, int32_t *d_len,
                               int32_t *d_dist_win, void *stream) {
   return solutions_launch(h, "pcgrl_solutions_for_grids", false, n, d_grids, cap, d_moves, d_len, d_dist_win, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- measures and diversity
+// include/pcgrl_amd_measures.h; kernels in measures/pcgrl_measures.h
+static const char *MEASURES_3D =
+    ": 2-D problems only (the reference's get_counts reads an attribute the 3-D maze does not have and get_co looks at two "
+    "axes only)";
+
+int32_t pcgrl_measures_tiles(pcgrl_handle h) {
+  if (!h) return -1;
+  return h->p.cfg.ndim == 2 ? h->p.n_tiles : 0;
+}
+
+static void meas_args_for(pcgrl_handle h, int32_t n, const uint8_t *d_grids, MeasArgs &a) {
+  a = MeasArgs{};
+  a.grids = d_grids;
+  a.n = n;
+  a.T = h->p.n_tiles;
+  a.P = meas_planes(h->p.n_tiles);
+  a.NW = (h->p.cfg.dims[0] * h->p.cfg.dims[1] + 63) / 64;
+  a.group = 1;
+}
+
+static int measures_launch(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
+                           int32_t *d_match, double *d_forms, double *d_entropy, const double *d_tab, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (h->p.cfg.ndim != 2) return fail(PCGRL_EUNSUPPORTED, std::string(who) + MEASURES_3D);
+  if (n < 0 || (n > 0 && (!d_counts || !d_match || (d_entropy && !d_tab) || (!own && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (n == 0) return PCGRL_OK;
+  ON_DEVICE(h->device);
+  MeasArgs a;
+  meas_args_for(h, n, own ? nullptr : d_grids, a);
+  a.counts = d_counts;
+  a.match = d_match;
+  a.forms = d_forms;
+  a.entropy = d_entropy;
+  a.tab = d_tab;
+  HIPCHK(launch_measures(h->p, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_measures(pcgrl_handle h, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
+                   const double *d_entropy_tab, void *stream) {
+  return measures_launch(h, "pcgrl_measures", true, h ? h->p.n_envs : 0, nullptr, d_counts, d_match, d_forms, d_entropy,
+                         d_entropy_tab, stream);
+}
+
+int pcgrl_measures_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
+                             double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
+  return measures_launch(h, "pcgrl_measures_for_grids", false, n, d_grids, d_counts, d_match, d_forms, d_entropy, d_entropy_tab,
+                         stream);
+}
+
+size_t pcgrl_diversity_scratch_bytes(pcgrl_handle h, int32_t n) {
+  if (!h || n <= 0 || h->p.cfg.ndim != 2) return 0;
+  // the bit-plane image, then one nearest-map key per map
+  return (size_t)n * (meas_planes(h->p.n_tiles) * ((h->p.cfg.dims[0] * h->p.cfg.dims[1] + 63) / 64) + 1) * sizeof(uint64_t);
+}
+
+// pack the n maps -- the engine's own or the caller's -- into d_scratch, then the all-pairs kernel per group
+static int diversity_launch(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t group,
+                            void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
+                            int32_t *d_pairwise, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (h->p.cfg.ndim != 2) return fail(PCGRL_EUNSUPPORTED, std::string(who) + MEASURES_3D);
+  if (n < 0 || (n > 0 && (!d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum || (!own && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (group < 2 || n % group != 0)
+    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
+  if (n == 0) return PCGRL_OK;
+  ON_DEVICE(h->device);
+  MeasArgs a;
+  meas_args_for(h, n, own ? nullptr : d_grids, a);
+  a.pack = (uint64_t *)d_scratch;
+  a.sum = (unsigned long long *)d_sum;
+  a.near_key = (unsigned long long *)(a.pack + (size_t)n * a.P * a.NW);
+  a.group = group;
+  HIPCHK(launch_measures(h->p, a, (hipStream_t)stream));
+  DivArgs d;
+  d.pack = a.pack;
+  d.n = n;
+  d.K = group;
+  d.P = a.P;
+  d.NW = a.NW;
+  div_splits(n, group, d.splits, d.tiles_per_split);
+  d.sum = a.sum;
+  d.near_key = a.near_key;
+  d.pairwise = d_pairwise;
+  HIPCHK(launch_diversity(d, (hipStream_t)stream));
+  if (d_scores || d_nearest || d_nearest_idx)
+    HIPCHK(launch_diversity_finish(d, h->p.cfg.dims[0] * h->p.cfg.dims[1], d_nearest, d_nearest_idx, d_scores,
+                                   (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_diversity(pcgrl_handle h, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
+                    int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  return diversity_launch(h, "pcgrl_diversity", true, h ? h->p.n_envs : 0, nullptr, group, d_scratch, d_sum, d_scores, d_nearest,
+                          d_nearest_idx, d_pairwise, stream);
+}
+
+int pcgrl_diversity_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch, int64_t *d_sum,
+                              double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  return diversity_launch(h, "pcgrl_diversity_for_grids", false, n, d_grids, group, d_scratch, d_sum, d_scores, d_nearest,
+                          d_nearest_idx, d_pairwise, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- multi-agent turtle stepping

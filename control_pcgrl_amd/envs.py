@@ -187,6 +187,16 @@ class PcgrlGymEnv:
         directions = ({"x": -1, "y": 0}, {"x": 1, "y": 0}, {"x": 0, "y": -1}, {"x": 0, "y": 1})  # engine.py:3
         return [dict(directions[m]) for m in s.moves[0, :n].cpu().tolist()]
 
+    @property
+    def measures(self):
+        """The behaviour characteristics of the current map under get_bc's names (evo/evolve.py:606-635): "emptiness",
+        "entropy", "symmetry", "symmetry-horizontal", "symmetry-vertical", "co-occurance" as Python floats, and
+        "tile_fractions", get_counts' list (evolve.py:449-464)."""
+        m = self._vec.measures()
+        out = {k: float(v[0].item()) for k, v in m.bc.items()}
+        out["tile_fractions"] = [float(x) for x in m.tile_fractions[0].cpu().tolist()]
+        return out
+
     def close(self):
         self._vec.close()
 

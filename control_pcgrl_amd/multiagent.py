@@ -160,6 +160,17 @@ class MultiAgentVecEnv:
     def paths(self, cap=None, overlay=False):
         return self._base.paths(cap=cap, overlay=overlay)
 
+    _NO_MEASURES = ("measures / diversity of a multi-agent batch: the reference computes them only in its single-agent evolution "
+                    "and evaluation loops (evo/evolve.py, rl/evaluate_ctrl.py) and they are not tested here on multi-agent "
+                    "engines -- hand get_state().grids to a single-agent VecPcgrlEnv's measures_for_grids / "
+                    "diversity_for_grids")
+
+    def measures(self, entropy=True):
+        raise NotImplementedError(self._NO_MEASURES)
+
+    def diversity(self, group=None, pairwise=False):
+        raise NotImplementedError(self._NO_MEASURES)
+
     def state_dict(self):
         """The engine's state image (VecPcgrlEnv.state_dict) plus the side record: positions, done bits and the generator's kept
         half, last statistics.  A restored env continues bit-identically, also mid-episode with some agents done."""

@@ -208,6 +208,7 @@ class VecPcgrlEnv:
         _lib.check(L.pcgrl_create(C.byref(self.cfg), self.num_envs, dev_index, C.byref(h)), "pcgrl_create")
         self._h = h
         self._L = L
+        self._entropy_tab = None  # measures(): built at first use
         self._dev_index = dev_index
         shape = (C.c_int32 * 4)()
         nd = C.c_int32()
@@ -695,6 +696,112 @@ class VecPcgrlEnv:
         g = torch.as_tensor(grids, device=self.device).to(torch.uint8).contiguous()
         return self._solutions(g.numel() // self.n_cells, g, cap, dist_win)
 
+    # -- level measures and pairwise Hamming diversity (include/pcgrl_amd_measures.h) ------------------------------------
+    def _entropy_table(self):
+        """tab[c] = (c / n) * ln(c / n) for c = 0 .. n, then get_entropy's max_val (evolve.py:436): built once per engine on
+        the host with numpy's scalar log -- the very operations of get_entropy (evolve.py:441-444) -- and uploaded at first use"""
+        if self._entropy_tab is None:
+            n, T = self.n_cells, self.spec.n_tiles
+            tab = np.zeros(n + 2, dtype=np.float64)
+            for c in range(1, n + 1):
+                p = np.int64(c) / n
+                tab[c] = p * np.log(p)
+            tab[n + 1] = -(1 / T) * np.log(1 / T) * T
+            self._entropy_tab = torch.from_numpy(tab).to(self.device)
+        return self._entropy_tab
+
+    def _measures_supported(self):
+        if len(self.map_shape) != 2:  # (the entry point refuses the 3-D maze before it looks at its pointers: its reason)
+            _lib.check(self._L.pcgrl_measures(self._h, None, None, None, None, None, None), "pcgrl_measures")
+
+    def _measures(self, n, grids, entropy):
+        self._measures_supported()
+        dev, T = self.device, self.spec.n_tiles
+        out = SimpleNamespace(counts=torch.empty((n, T), dtype=torch.int32, device=dev),
+                              match=torch.empty((n, 3), dtype=torch.int32, device=dev),
+                              forms=torch.empty((n, 5 + T), dtype=torch.float64, device=dev),
+                              entropy=torch.empty(n, dtype=torch.float64, device=dev) if entropy else None)
+        ent = out.entropy.data_ptr() if entropy else None
+        tab = self._entropy_table().data_ptr() if entropy else None
+        if grids is None:
+            _lib.check(self._L.pcgrl_measures(self._h, out.counts.data_ptr(), out.match.data_ptr(), out.forms.data_ptr(), ent, tab,
+                                              self._stream()), "pcgrl_measures")
+        else:
+            _lib.check(self._L.pcgrl_measures_for_grids(self._h, n, grids.data_ptr(), out.counts.data_ptr(),
+                                                        out.match.data_ptr(), out.forms.data_ptr(), ent, tab, self._stream()),
+                       "pcgrl_measures_for_grids")
+        # the float64 forms come from the kernel (correctly rounded divisions in the reference's order; torch's division by
+        # a scalar multiplies by its reciprocal, which is an ulp off now and then): views of its rows
+        f = out.forms
+        out.tile_fractions = f[:, 5:]  # get_counts (evolve.py:461-464)
+        out.bc = {"emptiness": f[:, 0], "symmetry-horizontal": f[:, 1], "symmetry-vertical": f[:, 2], "symmetry": f[:, 3],
+                  "co-occurance": f[:, 4]}
+        if entropy:
+            out.bc["entropy"] = out.entropy
+        out.emptiness = out.bc["emptiness"]
+        return out
+
+    def measures(self, entropy=True):
+        """The behaviour characteristics of every env's current map that the reference computes from the integer map
+        (evo/evolve.py:606-635 get_bc -> :423-592):
+          counts          int32 [N, T]    cells per tile type
+          match           int32 [N, 3]    horizontal matches, vertical matches, wrapped co-occurance matches
+          tile_fractions  float64 [N, T]  get_counts
+          bc              dict keyed by get_bc's names -> float64 [N]: "emptiness", "entropy" (entropy=True), "symmetry",
+                          "symmetry-horizontal", "symmetry-vertical", "co-occurance" (also .entropy, .emptiness)
+        All but entropy equal the reference bit for bit; entropy does on the host whose numpy built the table.  A function of
+        the maps alone (stale statistics do not matter); one kernel launch on the current stream, no host sync.  The 3-D maze: NotImplementedError."""
+        return self._measures(self.num_envs, None, entropy)
+
+    def measures_for_grids(self, grids, entropy=True):
+        """measures() of caller maps (any number of them, uint8 tile ids of this env's problem and map shape)."""
+        g = torch.as_tensor(grids, device=self.device).to(torch.uint8).contiguous()
+        return self._measures(g.numel() // self.n_cells, g, entropy)
+
+    def _diversity(self, n, grids, group, pairwise):
+        self._measures_supported()
+        K = n if group is None else int(group)
+        dev = self.device
+        if K < 2 or n % K:
+            raise ValueError(f"diversity: group = {K} must be at least 2 and divide the {n} maps")
+        G = n // K
+        scratch = torch.empty(max(1, int(self._L.pcgrl_diversity_scratch_bytes(self._h, n)) // 8), dtype=torch.int64, device=dev)
+        out = SimpleNamespace(hamming_sum=torch.empty(G, dtype=torch.int64, device=dev),
+                              scores=torch.empty((G, 2), dtype=torch.float64, device=dev),
+                              nearest=torch.empty(n, dtype=torch.int32, device=dev),
+                              nearest_idx=torch.empty(n, dtype=torch.int32, device=dev),
+                              pairwise=torch.empty((G, K, K), dtype=torch.int32, device=dev) if pairwise else None)
+        pw = out.pairwise.data_ptr() if pairwise else None
+        if grids is None:
+            _lib.check(self._L.pcgrl_diversity(self._h, K, scratch.data_ptr(), out.hamming_sum.data_ptr(), out.scores.data_ptr(),
+                                               out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw, self._stream()),
+                       "pcgrl_diversity")
+        else:
+            _lib.check(self._L.pcgrl_diversity_for_grids(self._h, n, grids.data_ptr(), K, scratch.data_ptr(),
+                                                         out.hamming_sum.data_ptr(), out.scores.data_ptr(),
+                                                         out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw, self._stream()),
+                       "pcgrl_diversity_for_grids")
+        out.div_score = out.scores[:, 0]  # div_calc (evaluate_ctrl.py:42-48)
+        out.diversity_bonus = out.scores[:, 1]  # evolve.py:1236-1244: N * N - 1, not N * (N - 1)
+        return out
+
+    def diversity(self, group=None, pairwise=False):
+        """Pairwise Hamming distances (cells whose tiles differ) among the envs' current maps, in consecutive groups of `group`
+        maps (None: one group of all of them):
+          hamming_sum      int64 [G]      the sum over all ordered pairs of a group
+          nearest          int32 [N]      the distance to the nearest other map of the group
+          nearest_idx      int32 [N]      that map's index within the group, the lowest on ties
+          div_score        float64 [G]    div_calc (rl/evaluate_ctrl.py:42-48)
+          diversity_bonus  float64 [G]    evo/evolve.py:1236-1244 (its denominator is K * K - 1)
+          pairwise         int32 [G, K, K] (pairwise=True), else None
+        Three kernel launches (pack, all pairs, finish) on the current stream, no host sync.  The 3-D maze: NotImplementedError."""
+        return self._diversity(self.num_envs, None, group, pairwise)
+
+    def diversity_for_grids(self, grids, group=None, pairwise=False):
+        """diversity() of caller maps (any number of them, uint8 tile ids of this env's problem and map shape)."""
+        g = torch.as_tensor(grids, device=self.device).to(torch.uint8).contiguous()
+        return self._diversity(g.numel() // self.n_cells, g, group, pairwise)
+
     # -- episodic-return reduction (rl/callbacks.py:91-117 on_episode_end, summed over the batch) -------------------
     def reduce_episodes(self, clear=True, out=None):
         """float64 [3 + n_stats] on the env's GPU: sum of returns, sum of lengths, number of episodes, sum of final
@@ -861,6 +968,22 @@ class SubBatchedVecEnv:
     def solutions(self, cap=None, dist_win=False):
         return self._cat(self._each(lambda i, e: e.solutions(cap=cap, dist_win=dist_win)),
                          ("moves", "length") + (("dist_win",) if dist_win else ()), dist_win=None)
+
+    def measures(self, entropy=True):
+        parts = self._each(lambda i, e: e.measures(entropy=entropy))
+        out = self._cat(parts, ("counts", "match", "forms") + (("entropy",) if entropy else ()), entropy=None)
+        f = out.forms
+        out.tile_fractions = f[:, 5:]
+        out.bc = {"emptiness": f[:, 0], "symmetry-horizontal": f[:, 1], "symmetry-vertical": f[:, 2], "symmetry": f[:, 3],
+                  "co-occurance": f[:, 4]}
+        if entropy:
+            out.bc["entropy"] = out.entropy
+        out.emptiness = out.bc["emptiness"]
+        return out
+
+    def diversity(self, group=None, pairwise=False):
+        raise NotImplementedError("diversity over sub-batches: a group could straddle two engines -- gather the maps "
+                                  "(get_state().grids) and call envs[0].diversity_for_grids(grids, group)")
 
     def reduce_episodes(self, clear=True):
         return torch.stack(self._each(lambda i, e: e.reduce_episodes(clear=clear))).sum(0)
