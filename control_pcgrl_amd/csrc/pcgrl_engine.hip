@@ -27,12 +27,14 @@
 #include "solutions/pcgrl_solutions.h"  // sokoban solutions (the move list behind sol-length)
 #include "multiagent/pcgrl_multiagent.h"  // multi-agent turtle stepping (binary, zelda)
 #include "measures/pcgrl_measures.h"  // level measures and pairwise Hamming diversity of 2-D maps
+#include "smb/pcgrl_smb.h"            // Super Mario Bros levels: statistics and A* play-through
 #include "../../include/pcgrl_amd_codes.h"
 #include "../../include/pcgrl_amd_async3d.h"
 #include "../../include/pcgrl_amd_paths.h"
 #include "../../include/pcgrl_amd_solutions.h"
 #include "../../include/pcgrl_amd_multiagent.h"
 #include "../../include/pcgrl_amd_measures.h"
+#include "../../include/pcgrl_amd_smb.h"
 
 using namespace pcgrl;
 
@@ -2111,6 +2113,62 @@ int pcgrl_ma_set_state(pcgrl_handle h, const uint8_t *d_mask, const int32_t *d_p
   a.in_side = d_side;
   a.in_stats = d_last_stats;
   HIPCHK(launch_ma(MA_SET_STATE, p, h->lpe, a, 0, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Super Mario Bros levels
+// include/pcgrl_amd_smb.h; kernel in smb/pcgrl_smb.h.  No handle: the evaluation is a function of the maps and the config.
+static int smb_check_shape(const char *who, int32_t h, int32_t w, int32_t power) {
+  if (h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 4..16 rows and 1..128 columns only (with fewer than 4 rows the "
+                                                       "reference's level has no exit)");
+  if (power < 1 || power > SMB_MAX_POWER)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": solver_power must be in [1, " + std::to_string(SMB_MAX_POWER) + "]");
+  return PCGRL_OK;
+}
+
+int64_t pcgrl_smb_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t solver_power) {
+  if (n < 1 || smb_check_shape("pcgrl_smb_workspace_bytes", h, w, solver_power) != PCGRL_OK) return -1;
+  return (int64_t)n * smb_ws_stride(solver_power);
+}
+
+int pcgrl_smb_evaluate(const pcgrl_smb_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace, int64_t workspace_bytes,
+                       int32_t cap, int32_t jump_cap, int32_t *d_stats, double *d_loss, int8_t *d_moves, int32_t *d_length,
+                       int16_t *d_jump_locs, int32_t *d_play, uint32_t *d_error, void *stream) {
+  const char *who = "pcgrl_smb_evaluate";
+  if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (cap < 0 || jump_cap < 0 || (d_moves && cap < 1) || (d_jump_locs && jump_cap < 1))
+    return fail(PCGRL_EINVAL, std::string(who) + ": cap and jump_cap must be at least 1 where their output is given");
+  const int rc = smb_check_shape(who, cfg->h, cfg->w, cfg->solver_power);
+  if (rc != PCGRL_OK) return rc;
+  const int64_t stride = smb_ws_stride(cfg->solver_power);
+  if (!d_workspace || ((uintptr_t)d_workspace & 7u) || workspace_bytes < (int64_t)n * stride)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 8-byte aligned or smaller than "
+                                                 "pcgrl_smb_workspace_bytes");
+  SmbArgs a = {};
+  a.h = cfg->h;
+  a.w = cfg->w;
+  a.power = cfg->solver_power;
+  a.n = n;
+  a.grids = d_grids;
+  a.ws = (uint8_t *)d_workspace;
+  a.ws_stride = stride;
+  a.cap = cap;
+  a.jump_cap = jump_cap;
+  a.stats = d_stats;
+  a.loss = d_loss;
+  a.moves = d_moves;
+  a.length = d_length;
+  a.jump_locs = d_jump_locs;
+  a.play = d_play;
+  a.error = d_error;
+  for (int k = 0; k < SMB_STATS; k++) {
+    a.has_trg[k] = cfg->has_trg[k];
+    a.weight[k] = cfg->weight[k];
+    a.trg_lo[k] = cfg->trg_lo[k];
+    a.trg_hi[k] = cfg->trg_hi[k];
+  }
+  HIPCHK(launch_smb(a, (hipStream_t)stream));
   return PCGRL_OK;
 }
 
