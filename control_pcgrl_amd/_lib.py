@@ -14,11 +14,11 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "codes/pcgrl_codes.hip", "reps3d/pcgrl_k_3d_turtle.hip", "reps3d/pcgrl_k_3d_wide.hip",
          "async3d/pcgrl_k_3d_async.hip", "paths/pcgrl_k_paths_binary.hip", "paths/pcgrl_k_paths_zelda.hip",
          "solutions/pcgrl_k_solutions.hip", "multiagent/pcgrl_k_ma_binary.hip", "multiagent/pcgrl_k_ma_zelda.hip",
-         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip"]
+         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
-           "smb/pcgrl_smb.h"]
+           "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -28,6 +28,7 @@ SOLUTIONS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_so
 MULTIAGENT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_multiagent.h")
 MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_measures.h")
 SMB_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb.h")
+SMB_ENV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_env.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -179,13 +180,39 @@ SMB_SYMBOLS = {
 }
 
 
+# include/pcgrl_amd_smb_env.h: stepping Super Mario Bros environments (narrow, turtle; a handle of its own)
+class PcgrlSmbEnvConfig(C.Structure):
+    _fields_ = [
+        ("h", C.c_int32), ("w", C.c_int32), ("representation", C.c_int32), ("obs_window", C.c_int32 * 2),
+        ("max_iterations", C.c_int32), ("max_changes", C.c_int32), ("solver_power", C.c_int32), ("n_envs", C.c_int32),
+        ("has_trg", C.c_int32 * PCGRL_SMB_STATS), ("weight", C.c_double * PCGRL_SMB_STATS),
+        ("trg_lo", C.c_double * PCGRL_SMB_STATS), ("trg_hi", C.c_double * PCGRL_SMB_STATS),
+    ]
+
+
+SMB_ENV_SYMBOLS = {
+    "pcgrl_smb_env_workspace_bytes": (C.c_int64, [C.POINTER(PcgrlSmbEnvConfig)]),
+    "pcgrl_smb_env_obs_bytes": (C.c_int64, [C.POINTER(PcgrlSmbEnvConfig)]),
+    "pcgrl_smb_env_create": (C.c_int, [C.POINTER(PcgrlSmbEnvConfig), C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "pcgrl_smb_env_destroy": (None, [C.c_void_p]),
+    "pcgrl_smb_env_seed": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_env_reset": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "pcgrl_smb_env_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
+    "pcgrl_smb_env_observe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_env_get_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 8),
+    "pcgrl_smb_env_get_last_episode": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "pcgrl_smb_env_poll_error": (C.c_int, [C.c_void_p]),
+}
+
+
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
     parallel, then linked into the shared library.  Rebuilds when a source is newer than the library.
     `out` / `defines`: development builds (tools/phase_timing.py, tools/wave_trace.py)."""
     out = out or LIB_PATH
     srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER, ASYNC3D_HEADER, PATHS_HEADER,
-                                                       SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER, SMB_HEADER]
+                                                       SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER, SMB_HEADER,
+                                                       SMB_ENV_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -196,7 +223,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     hdr_time = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     hdr_time = max(hdr_time, os.path.getmtime(HEADER), os.path.getmtime(CODES_HEADER), os.path.getmtime(ASYNC3D_HEADER),
                    os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER),
-                   os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER))
+                   os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER), os.path.getmtime(SMB_ENV_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -243,7 +270,7 @@ def lib():
         for name, (res, args) in (list(SYMBOLS.items()) + list(CODES_SYMBOLS.items()) + list(ASYNC3D_SYMBOLS.items())
                                   + list(PATHS_SYMBOLS.items()) + list(SOLUTIONS_SYMBOLS.items())
                                   + list(MULTIAGENT_SYMBOLS.items()) + list(MEASURES_SYMBOLS.items())
-                                  + list(SMB_SYMBOLS.items())):
+                                  + list(SMB_SYMBOLS.items()) + list(SMB_ENV_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

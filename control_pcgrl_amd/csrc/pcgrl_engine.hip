@@ -35,6 +35,8 @@
 #include "../../include/pcgrl_amd_multiagent.h"
 #include "../../include/pcgrl_amd_measures.h"
 #include "../../include/pcgrl_amd_smb.h"
+#include "../../include/pcgrl_amd_smb_env.h"
+#include "smb/pcgrl_smb_env.h"
 
 using namespace pcgrl;
 
@@ -2169,6 +2171,225 @@ int pcgrl_smb_evaluate(const pcgrl_smb_config *cfg, int32_t n, const uint8_t *d_
     a.trg_hi[k] = cfg->trg_hi[k];
   }
   HIPCHK(launch_smb(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- Super Mario Bros environments
+// include/pcgrl_amd_smb_env.h; kernels in smb/pcgrl_smb_env.h.  A handle of its own: the engine above does not know the problem.
+
+struct pcgrl_smb_env {
+  pcgrl_smb_env_config cfg;
+  int device = 0;
+  SmbEnvArgs a = {};
+  std::vector<void *> allocs;
+};
+
+static int smb_env_check(const char *who, const pcgrl_smb_env_config *c) {
+  if (!c) return fail(PCGRL_EINVAL, std::string(who) + ": null config");
+  const int rc = smb_check_shape(who, c->h, c->w, c->solver_power);
+  if (rc != PCGRL_OK) return rc;
+  if (c->representation == PCGRL_REP_WIDE)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": the wide representation is not stepped for smb (the reference's wide "
+                                                       "fails on a non-square map: wide_rep.py:42, IndexError)");
+  if (c->representation != PCGRL_REP_NARROW && c->representation != PCGRL_REP_TURTLE)
+    return fail(PCGRL_EINVAL, std::string(who) + ": unknown representation");
+  for (int k = 0; k < 2; k++)
+    if (c->obs_window[k] < 1 || c->obs_window[k] > 255)
+      return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": obs_window entries must be in 1..255 (the reference keeps the pad as "
+                                                         "int8 and fails above: 'index can't contain negative values')");
+  if (c->n_envs < 1 || c->max_iterations < 0 || c->max_changes < -1)
+    return fail(PCGRL_EINVAL, std::string(who) + ": n_envs must be at least 1, max_iterations >= 0 and max_changes >= -1");
+  return PCGRL_OK;
+}
+
+extern "C" {
+
+int64_t pcgrl_smb_env_workspace_bytes(const pcgrl_smb_env_config *cfg) {
+  if (smb_env_check("pcgrl_smb_env_workspace_bytes", cfg) != PCGRL_OK) return -1;
+  return (int64_t)cfg->n_envs * smb_ws_stride(cfg->solver_power);
+}
+
+int64_t pcgrl_smb_env_obs_bytes(const pcgrl_smb_env_config *cfg) {
+  if (smb_env_check("pcgrl_smb_env_obs_bytes", cfg) != PCGRL_OK) return -1;
+  return (int64_t)cfg->obs_window[0] * cfg->obs_window[1] * (SMB_TILES + 1);
+}
+
+int pcgrl_smb_env_create(const pcgrl_smb_env_config *cfg, int32_t device, void *d_workspace, int64_t workspace_bytes,
+                         pcgrl_smb_env_handle *out) {
+  const char *who = "pcgrl_smb_env_create";
+  if (!out) return fail(PCGRL_EINVAL, std::string(who) + ": null out");
+  const int rc = smb_env_check(who, cfg);
+  if (rc != PCGRL_OK) return rc;
+  const int64_t stride = smb_ws_stride(cfg->solver_power);
+  if (!d_workspace || ((uintptr_t)d_workspace & 7u) || workspace_bytes < (int64_t)cfg->n_envs * stride)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 8-byte aligned or smaller than "
+                                                 "pcgrl_smb_env_workspace_bytes");
+  if (device < 0) return fail(PCGRL_EINVAL, std::string(who) + ": bad device");
+  ON_DEVICE(device);
+  pcgrl_smb_env *e = new pcgrl_smb_env();
+  e->cfg = *cfg;
+  e->device = device;
+  SmbEnvArgs &a = e->a;
+  a.h = cfg->h;
+  a.w = cfg->w;
+  a.rep = cfg->representation;
+  a.oh = cfg->obs_window[0];
+  a.ow = cfg->obs_window[1];
+  a.max_iterations = cfg->max_iterations;
+  a.max_changes = cfg->max_changes;
+  a.power = cfg->solver_power;
+  a.n = cfg->n_envs;
+  a.map_stride = (cfg->h * cfg->w + 15) / 16 * 16;
+  a.ws = (uint8_t *)d_workspace;
+  a.ws_stride = stride;
+  for (int k = 0; k < SMB_STATS; k++) {
+    a.has_trg[k] = cfg->has_trg[k];
+    a.weight[k] = cfg->weight[k];
+    a.trg_lo[k] = cfg->trg_lo[k];
+    a.trg_hi[k] = cfg->trg_hi[k];
+  }
+  const int cells = cfg->h * cfg->w, cpl = (cells + 63) / 64;
+  const std::vector<JumpEntry> jt = make_jump_table(64, cpl, cells);
+  const size_t n = (size_t)cfg->n_envs;
+  auto alloc = [&](void **ptr, size_t bytes) {
+    hipError_t he = hipMalloc(ptr, bytes);
+    if (he == hipSuccess) {
+      e->allocs.push_back(*ptr);
+      he = hipMemset(*ptr, 0, bytes);
+    }
+    return he;
+  };
+  hipError_t he = alloc((void **)&a.maps, n * a.map_stride);
+  if (he == hipSuccess) he = alloc((void **)&a.st, n * sizeof(SmbEnvState));
+  if (he == hipSuccess) he = alloc((void **)&a.rng, n * sizeof(RngState));
+  if (he == hipSuccess) he = alloc((void **)&a.jump, jt.size() * sizeof(JumpEntry));
+  if (he == hipSuccess) he = alloc((void **)&a.err, 4 * sizeof(int32_t));
+  if (he == hipSuccess) he = hipMemcpy((void *)a.jump, jt.data(), jt.size() * sizeof(JumpEntry), hipMemcpyHostToDevice);
+  if (he != hipSuccess) {
+    pcgrl_smb_env_destroy(e);
+    return fail(PCGRL_EHIP, std::string(who) + ": " + hipGetErrorString(he));
+  }
+  *out = e;
+  std::vector<uint64_t> seeds(n);
+  for (size_t i = 0; i < n; i++) seeds[i] = (uint64_t)i;
+  return pcgrl_smb_env_seed(e, seeds.data());
+}
+
+void pcgrl_smb_env_destroy(pcgrl_smb_env_handle h) {
+  if (!h) return;
+  DeviceGuard guard(h->device);
+  for (void *p : h->allocs) (void)hipFree(p);
+  delete h;
+}
+
+int pcgrl_smb_env_seed(pcgrl_smb_env_handle h, const uint64_t *seeds) {
+  if (!h || !seeds) return fail(PCGRL_EINVAL, "pcgrl_smb_env_seed: bad arguments");
+  ON_DEVICE(h->device);
+  std::vector<RngState> r(h->a.n);
+  for (int i = 0; i < h->a.n; i++) {
+    pcg64_seed_state(seeds[i], r[i].rep);
+    memcpy(r[i].prob, r[i].rep, sizeof(r[i].rep));  // envs/pcgrl_env.py:142-146: the same seed for both streams
+  }
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(h->a.rng, r.data(), r.size() * sizeof(RngState), hipMemcpyHostToDevice));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_env_reset(pcgrl_smb_env_handle h, const uint8_t *d_mask, const uint8_t *d_init_grids, const int32_t *d_init_pos,
+                        uint8_t *d_obs, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_env_reset: null handle");
+  if ((uintptr_t)d_obs & 15u) return fail(PCGRL_EINVAL, "pcgrl_smb_env_reset: the observation must be 16-byte aligned");
+  if (d_init_pos && !d_init_grids) return fail(PCGRL_EINVAL, "pcgrl_smb_env_reset: init_pos needs init_grids");
+  ON_DEVICE(h->device);
+  SmbEnvArgs a = h->a;
+  a.mask = d_mask;
+  a.init_grids = d_init_grids;
+  a.init_pos = d_init_pos;
+  a.obs = d_obs;
+  HIPCHK(launch_smb_env(SMB_ENV_RESET, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_env_step(pcgrl_smb_env_handle h, const int32_t *d_actions, int32_t auto_reset, uint8_t *d_obs, float *d_reward,
+                       double *d_reward64, uint8_t *d_done, int32_t *d_stats, void *stream) {
+  if (!h || !d_actions) return fail(PCGRL_EINVAL, "pcgrl_smb_env_step: null handle or actions");
+  if ((uintptr_t)d_obs & 15u) return fail(PCGRL_EINVAL, "pcgrl_smb_env_step: the observation must be 16-byte aligned");
+  ON_DEVICE(h->device);
+  SmbEnvArgs a = h->a;
+  a.actions = d_actions;
+  a.auto_reset = auto_reset ? 1 : 0;
+  a.obs = d_obs;
+  a.reward = d_reward;
+  a.reward64 = d_reward64;
+  a.done = d_done;
+  a.stats_out = d_stats;
+  HIPCHK(launch_smb_env(SMB_ENV_STEP, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_env_observe(pcgrl_smb_env_handle h, uint8_t *d_obs, void *stream) {
+  if (!h || !d_obs) return fail(PCGRL_EINVAL, "pcgrl_smb_env_observe: bad arguments");
+  if ((uintptr_t)d_obs & 15u) return fail(PCGRL_EINVAL, "pcgrl_smb_env_observe: the observation must be 16-byte aligned");
+  ON_DEVICE(h->device);
+  SmbEnvArgs a = h->a;
+  a.obs = d_obs;
+  HIPCHK(launch_smb_env(SMB_ENV_OBSERVE, a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+static SmbEnvGather smb_env_gather_of(pcgrl_smb_env_handle h) {
+  SmbEnvGather g = {};
+  g.n = h->a.n;
+  g.h = h->a.h;
+  g.w = h->a.w;
+  g.map_stride = h->a.map_stride;
+  g.maps = h->a.maps;
+  g.st = h->a.st;
+  return g;
+}
+
+int pcgrl_smb_env_get_state(pcgrl_smb_env_handle h, uint8_t *d_grids, int32_t *d_pos, int32_t *d_counters, int32_t *d_stats,
+                            double *d_last_loss, double *d_ep_return, int64_t *d_iterations, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_env_get_state: null handle");
+  ON_DEVICE(h->device);
+  SmbEnvGather g = smb_env_gather_of(h);
+  g.grids = d_grids;
+  g.pos = d_pos;
+  g.counters = d_counters;
+  g.stats = d_stats;
+  g.last_loss = d_last_loss;
+  g.ep_return = d_ep_return;
+  g.iters = d_iterations;
+  HIPCHK(launch_smb_env_gather(g, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_env_get_last_episode(pcgrl_smb_env_handle h, double *d_return, int32_t *d_length, int32_t *d_stats,
+                                   int32_t *d_count, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_env_get_last_episode: null handle");
+  ON_DEVICE(h->device);
+  SmbEnvGather g = smb_env_gather_of(h);
+  g.last_return = d_return;
+  g.last_len = d_length;
+  g.last_stats = d_stats;
+  g.last_count = d_count;
+  HIPCHK(launch_smb_env_gather(g, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_env_poll_error(pcgrl_smb_env_handle h) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_env_poll_error: null handle");
+  ON_DEVICE(h->device);
+  HIPCHK(hipDeviceSynchronize());
+  int32_t flags = 0;
+  HIPCHK(hipMemcpy(&flags, h->a.err, sizeof(flags), hipMemcpyDeviceToHost));
+  if (flags) {
+    HIPCHK(hipMemset(h->a.err, 0, sizeof(flags)));
+    if (flags & 1) return fail(PCGRL_EACTION, "an action was outside the action space (the reference raises IndexError)");
+    if (flags & 2) return fail(PCGRL_EINVAL, "smb: a tile id above 6 was seen in init_grids (read as empty)");
+  }
   return PCGRL_OK;
 }
 

@@ -5,7 +5,7 @@
 //
 // smb_kernel: one 64-lane wave per level.
 //   map       the level's bytes are staged in LDS (ids above 6 become 0 and raise error bit 0); smb_evaluate_level takes that
-//             LDS map, so a later step kernel can call it on the map it already holds.
+//             LDS map, so the step kernel of smb/pcgrl_smb_env.h calls it (or its scan half alone) on the map it already holds.
 //   scans     lane-parallel: a lane owns columns `lane` and `lane + 64` (W <= 128), walks each bottom-up once (nearest floor
 //             below for dist-floor, both neighbour comparisons for noise, the tube's two side neighbours, the two counts) and
 //             leaves the column's 16-bit solid mask in LDS; five wave reductions.
@@ -212,10 +212,10 @@ __device__ inline uint32_t smb_search(const uint16_t *col, uint32_t *seen, uint2
   return best;
 }
 
-// One level, by one 64-lane wave: the nine statistics and the play-through of the map in L.map ([H][W], ids 0..6).
-// nodes / heap: this level's workspace slot.  Every lane returns with the same SmbResult.
-__device__ inline void smb_evaluate_level(SmbLds &L, int H, int W, int power, uint2 *nodes, uint32_t *heap, const SmbPlayOut &out,
-                                          SmbResult &r) {
+// The scan half of a level's evaluation, by one 64-lane wave: the five map statistics of the map in L.map ([H][W], ids 0..6)
+// into r.stats[0..4], and the level's solid columns into L.col.  The step kernel of smb/pcgrl_smb_env.h calls it alone when an
+// edit left the level's solidity as it was (the play statistics keep their values then).
+__device__ inline void smb_scan_level(SmbLds &L, int H, int W, SmbResult &r) {
   const int lane = threadIdx.x & 63;
   int dist_floor = 0, tubes = 0, enemies = 0, empty = 0, noise = 0;
   for (int x = lane; x < W; x += 64) {
@@ -251,7 +251,13 @@ __device__ inline void smb_evaluate_level(SmbLds &L, int H, int W, int power, ui
   r.stats[2] = smb_wave_sum(enemies);
   r.stats[3] = smb_wave_sum(empty);
   r.stats[4] = smb_wave_sum(noise);
+}
 
+// The play half: the A* play-through of the level in L.col (smb_scan_level left it there) into r.stats[5..8] and the play record.
+// nodes / heap: this level's workspace slot.  Every lane returns with the same values.
+__device__ inline void smb_play_level(SmbLds &L, int H, int W, int power, uint2 *nodes, uint32_t *heap, const SmbPlayOut &out,
+                                      SmbResult &r) {
+  const int lane = threadIdx.x & 63;
   uint32_t fin = 0;
   int it1 = 0, it2 = 0, won = 0;
   for (int pass = 0; pass < 2; pass++) {
@@ -312,6 +318,15 @@ __device__ inline void smb_evaluate_level(SmbLds &L, int H, int W, int power, ui
     }
 }
 
+// One level, by one 64-lane wave: the nine statistics and the play-through of the map in L.map ([H][W], ids 0..6).
+// nodes / heap: this level's workspace slot.  Every lane returns with the same SmbResult.
+__device__ inline void smb_evaluate_level(SmbLds &L, int H, int W, int power, uint2 *nodes, uint32_t *heap, const SmbPlayOut &out,
+                                          SmbResult &r) {
+  smb_scan_level(L, H, W, r);
+  smb_play_level(L, H, W, power, nodes, heap, out, r);
+}
+
+#ifndef PCGRL_SMB_DEVICE_ONLY  // (smb/pcgrl_k_smb_env.hip takes the device functions above without a second smb_kernel)
 __global__ __launch_bounds__(64) void smb_kernel(const SmbArgs a) {
   __shared__ SmbLds L;
   const int lvl = blockIdx.x, lane = threadIdx.x;
@@ -361,6 +376,7 @@ __global__ __launch_bounds__(64) void smb_kernel(const SmbArgs a) {
     if (a.error) a.error[lvl] = err;
   }
 }
+#endif  // PCGRL_SMB_DEVICE_ONLY
 
 #endif  // PCGRL_KERNEL_TU
 

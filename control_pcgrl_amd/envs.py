@@ -206,6 +206,9 @@ def make_env(cfg, device="cuda:0"):
     rep = _cfg_get(cfg, "representation")
     if rep not in ("narrow", "turtle", "wide"):
         raise Exception("Unknown representation: {}".format(rep))  # rl/envs.py:65
+    if _cfg_get(cfg, "task.problem") == "smb":
+        from .smb_env import SmbGymEnv
+        return SmbGymEnv(cfg, device=device)
     if _cfg_get(cfg, "multiagent.n_agents", 0):  # rl/envs.py: MultiAgentWrapper, dict observations / actions
         from .multiagent import MultiAgentGymEnv
         return MultiAgentGymEnv(cfg, device=device)

@@ -127,6 +127,9 @@ class PcgrlVectorEnv(_Base):
         if vec is None and _cfg_get(cfg, "multiagent.n_agents", 0):
             raise NotImplementedError("PcgrlVectorEnv with multiagent.n_agents: RLlib's VectorEnv has one agent per sub-env; use "
                                       "multiagent.MultiAgentVecEnv (batched) or make_env(cfg) (the reference's dict call shape)")
+        if (vec is None and _cfg_get(cfg, "task.problem") == "smb") or type(vec).__name__ == "SmbVecEnv":
+            raise NotImplementedError("PcgrlVectorEnv with smb: the RLlib adapter drives VecPcgrlEnv's engine handle (host-mapped "
+                                      "outputs, masked resets per sub-env); step smb through SmbVecEnv or make_env(cfg)")
         self.vec = vec if vec is not None else make_vec_env(cfg, num_envs, device=device, seeds=seeds, auto_reset=False)
         v = self.vec
         assert not v.auto_reset, "PcgrlVectorEnv drives resets itself (RLlib calls reset_at)"

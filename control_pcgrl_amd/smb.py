@@ -2,8 +2,8 @@
 derives from them and the A* play-through behind the play statistics, for a batch of maps in one launch
 (include/pcgrl_amd_smb.h, csrc/smb/pcgrl_smb.h).
 
-Evaluation only: stepping SMB environments is not part of the engine, so PROBLEMS / problem_spec / build_config do not know
-"smb".  file:line references are relative to the reference's control_pcgrl/ directory.
+This module evaluates maps; smb_env.py steps SMB environments (SmbVecEnv) with the same kernels.  Neither is part of the 2-D
+engine, so PROBLEMS / problem_spec / build_config do not know "smb".  file:line references are relative to the reference's control_pcgrl/ directory.
 """
 import ctypes as C
 

@@ -1,0 +1,320 @@
+"""Stepping Super Mario Bros environments on the device: what make_env(cfg) of the reference does for smb with the narrow or
+the turtle representation -- reset, update, the nine statistics, reward, done, the cropped one-hot observation and the automatic
+reset -- for a batch of envs, one launch per step (include/pcgrl_amd_smb_env.h, csrc/smb/pcgrl_smb_env.h).
+
+SMB does not fit the 2-D engine (a map up to 128 columns of bytes, nine statistics), so this is an env class of its own next to
+the evaluator of smb.py: PROBLEMS / problem_spec / build_config still do not know "smb", and make_vec_env / make_env dispatch
+here on cfg.task.problem == "smb".  file:line references are relative to the reference's control_pcgrl/ directory.
+"""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+from .smb import MAX_H, MAX_SOLVER_POWER, MAX_W, MIN_H, SMB_TILES, smb_config, smb_spec
+
+REPS = {"narrow": 0, "turtle": 1}
+MAX_OBS_WINDOW = 255  # Cropped.set_pad_size keeps the pad as int8: the reference fails above
+
+
+def _refuse(what, why):
+    raise NotImplementedError(f"smb: {what} is not stepped on the device: {why}")
+
+
+class SmbVecEnv:
+    """N Mario envs on one device with VecPcgrlEnv's conventions: torch tensors in and out, one HIP launch per step(), output
+    tensors owned by the env and overwritten by the next call.  There is no CPU fallback.
+
+    step(actions) -> (obs uint8 [N][oh][ow][8], reward [N], done bool [N], truncated (= done), info); info["stats"] is int32
+    [N][9] (stat_keys order): the statistics after the step, of the finished episode where the step ended one.  With auto_reset a
+    finished env draws its next episode inside the same launch and the observation returned is that episode's first."""
+
+    def __init__(self, representation, map_shape=(16, 116), num_envs=1, device="cuda:0", obs_window=None, weights=None,
+                 max_board_scans=3, change_percentage=None, seeds=None, auto_reset=True, solver_power=10000,
+                 reward_dtype=torch.float32):
+        self._h = None
+        self._L = _lib.lib()
+        if representation == "wide":
+            _refuse("the wide representation", "the reference's wide fails on a non-square map (wide_rep.py:42, IndexError)")
+        if representation not in REPS:
+            raise ValueError(f"unknown representation {representation!r}")
+        map_shape = tuple(int(s) for s in map_shape)
+        if len(map_shape) != 2:
+            raise ValueError(f"smb maps are 2-D, got shape {map_shape}")
+        H, W = map_shape
+        if not (MIN_H <= H <= MAX_H and 1 <= W <= MAX_W) or not 1 <= int(solver_power) <= MAX_SOLVER_POWER:
+            raise NotImplementedError(f"smb: map_shape {map_shape} / solver_power {solver_power} outside {MIN_H}..{MAX_H} x "
+                                      f"1..{MAX_W} and 1..{MAX_SOLVER_POWER}")
+        obs_window = (2 * H, 2 * W) if obs_window is None else tuple(int(s) for s in obs_window)  # rl/utils.py:302-334
+        if len(obs_window) != 2 or min(obs_window) < 1:
+            raise ValueError(f"obs_window must be two positive sizes, got {obs_window}")
+        if max(obs_window) > MAX_OBS_WINDOW:
+            _refuse(f"obs_window {obs_window}", f"an entry above {MAX_OBS_WINDOW} fails in the reference (Cropped keeps the pad as "
+                    "int8: 'index can't contain negative values')")
+        if reward_dtype not in (torch.float32, torch.float64):
+            raise ValueError("reward_dtype must be torch.float32 or torch.float64")
+        if int(num_envs) < 1:
+            raise ValueError("num_envs must be at least 1")
+        self.representation, self.map_shape, self.obs_window = representation, map_shape, obs_window
+        self.num_envs, self.auto_reset, self.solver_power = int(num_envs), bool(auto_reset), int(solver_power)
+        self.spec = smb_spec(map_shape)
+        self.stat_keys = list(self.spec.stat_keys)
+        self.num_actions = len(SMB_TILES) if representation == "narrow" else 4 + len(SMB_TILES)
+        self.obs_shape = obs_window + (len(SMB_TILES) + 1,)
+        self.max_iterations = H * W * int(max_board_scans) + 1  # pcgrl_env.py:241
+        self.max_changes = None if change_percentage is None else max(int(change_percentage * H * W), 1)  # :235-239
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("SmbVecEnv needs a cuda device: there is no CPU fallback")
+        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        base = smb_config(map_shape, solver_power, weights)
+        cfg = _lib.PcgrlSmbEnvConfig()
+        cfg.h, cfg.w, cfg.representation = H, W, REPS[representation]
+        cfg.obs_window[0], cfg.obs_window[1] = obs_window
+        cfg.max_iterations = self.max_iterations
+        cfg.max_changes = -1 if self.max_changes is None else self.max_changes
+        cfg.solver_power, cfg.n_envs = self.solver_power, self.num_envs
+        for i in range(9):
+            cfg.has_trg[i], cfg.weight[i], cfg.trg_lo[i], cfg.trg_hi[i] = base.has_trg[i], base.weight[i], base.trg_lo[i], base.trg_hi[i]
+        self.cfg = cfg
+        self.weights = {k: float(cfg.weight[i]) for i, k in enumerate(self.stat_keys)}
+        nbytes = self._L.pcgrl_smb_env_workspace_bytes(C.byref(cfg))
+        if nbytes < 0:
+            raise NotImplementedError("smb: " + self._L.pcgrl_last_error().decode())
+        N, dev = self.num_envs, self.device
+        self._workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        h = C.c_void_p()
+        _lib.check(self._L.pcgrl_smb_env_create(C.byref(cfg), self._dev_index, self._workspace.data_ptr(), nbytes, C.byref(h)),
+                   "pcgrl_smb_env_create")
+        self._h = h
+        self._obs = torch.empty((N,) + self.obs_shape, dtype=torch.uint8, device=dev)
+        self._reward = torch.empty(N, dtype=reward_dtype, device=dev)
+        self._done = torch.empty(N, dtype=torch.bool, device=dev)
+        self._stats = torch.empty((N, 9), dtype=torch.int32, device=dev)
+        self._r32 = self._reward.data_ptr() if reward_dtype == torch.float32 else None
+        self._r64 = self._reward.data_ptr() if reward_dtype == torch.float64 else None
+        self._step_out = (self._obs, self._reward, self._done, self._done, {"stats": self._stats})
+        if seeds is not None:
+            self.seed(seeds)
+
+    def _stream(self):
+        try:
+            return torch._C._cuda_getCurrentRawStream(self._dev_index)
+        except AttributeError:  # pragma: no cover
+            return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("SmbVecEnv is closed")
+        return self._h
+
+    def seed(self, seeds):
+        """Env i gets numpy PCG64(SeedSequence(seeds[i])) for both RNG streams (envs/pcgrl_env.py:142-146)."""
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
+        _lib.check(self._L.pcgrl_smb_env_seed(self._handle(), s.ctypes.data), "pcgrl_smb_env_seed")
+
+    def reset(self, mask=None, init_grids=None, init_pos=None):
+        """Resets the envs of `mask` (all without one).  init_grids uint8 [N][H][W] replaces the drawn maps and draws nothing from
+        the streams, as VecPcgrlEnv.reset does; init_pos [N][2] is the turtle's start on them (narrow starts at cell 0)."""
+        def dev(t, dtype, shape):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, device=self.device).to(dtype).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
+            return t
+
+        N = self.num_envs
+        m = dev(mask, torch.uint8, (N,))
+        g = dev(init_grids, torch.uint8, (N,) + self.map_shape)
+        p = dev(init_pos, torch.int32, (N, 2))
+        if p is not None and g is None:
+            raise ValueError("init_pos needs init_grids")
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.pcgrl_smb_env_reset(self._handle(), m.data_ptr() if m is not None else None,
+                                                   g.data_ptr() if g is not None else None,
+                                                   p.data_ptr() if p is not None else None, self._obs.data_ptr(), self._stream()),
+                       "pcgrl_smb_env_reset")
+        return self._obs, {}
+
+    def step(self, actions):
+        if actions.numel() != self.num_envs:
+            raise ValueError(f"actions must be [{self.num_envs}], got {tuple(actions.shape)}")
+        if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
+            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        rc = self._L.pcgrl_smb_env_step(self._handle(), actions.data_ptr(), 1 if self.auto_reset else 0, self._obs.data_ptr(),
+                                        self._r32, self._r64, self._done.data_ptr(), self._stats.data_ptr(), self._stream())
+        if rc:
+            _lib.check(rc, "pcgrl_smb_env_step")
+        return self._step_out
+
+    def observe(self):
+        _lib.check(self._L.pcgrl_smb_env_observe(self._handle(), self._obs.data_ptr(), self._stream()), "pcgrl_smb_env_observe")
+        return self._obs
+
+    def get_state(self):
+        """grids uint8 [N][H][W], pos int32 [N][2], iteration, changes, n_step (narrow's scan counter), searches (play-throughs
+        run since the env was made), stats int32 [N][9], last_loss, ep_return float64 [N], search_iterations int64 [N] and
+        max_search_iterations (the most one call spent on the env)."""
+        N, dev = self.num_envs, self.device
+        grids = torch.empty((N,) + self.map_shape, dtype=torch.uint8, device=dev)
+        pos = torch.empty((N, 2), dtype=torch.int32, device=dev)
+        counters = torch.empty((N, 4), dtype=torch.int32, device=dev)
+        stats = torch.empty((N, 9), dtype=torch.int32, device=dev)
+        last_loss = torch.empty(N, dtype=torch.float64, device=dev)
+        ep_return = torch.empty(N, dtype=torch.float64, device=dev)
+        iters = torch.empty((N, 2), dtype=torch.int64, device=dev)
+        _lib.check(self._L.pcgrl_smb_env_get_state(self._handle(), grids.data_ptr(), pos.data_ptr(), counters.data_ptr(),
+                                                   stats.data_ptr(), last_loss.data_ptr(), ep_return.data_ptr(), iters.data_ptr(),
+                                                   self._stream()), "pcgrl_smb_env_get_state")
+        return SimpleNamespace(grids=grids, pos=pos, iteration=counters[:, 0], changes=counters[:, 1], n_step=counters[:, 2],
+                               searches=counters[:, 3], stats=stats, last_loss=last_loss, ep_return=ep_return,
+                               search_iterations=iters[:, 0], max_search_iterations=iters[:, 1])
+
+    def last_episode(self):
+        """The last finished episode of every env: ep_return float64 [N], length int32 [N], stats int32 [N][9], count int32 [N]
+        (how many episodes the env has finished; the other rows mean nothing while it is 0)."""
+        N, dev = self.num_envs, self.device
+        ret = torch.empty(N, dtype=torch.float64, device=dev)
+        length = torch.empty(N, dtype=torch.int32, device=dev)
+        stats = torch.empty((N, 9), dtype=torch.int32, device=dev)
+        count = torch.empty(N, dtype=torch.int32, device=dev)
+        _lib.check(self._L.pcgrl_smb_env_get_last_episode(self._handle(), ret.data_ptr(), length.data_ptr(), stats.data_ptr(),
+                                                          count.data_ptr(), self._stream()), "pcgrl_smb_env_get_last_episode")
+        return SimpleNamespace(ep_return=ret, length=length, stats=stats, count=count)
+
+    def set_solver_budget(self, budget):
+        _refuse("a solver budget", "the play-through is not resumable yet: a step launch lasts as long as its longest search")
+
+    def step_ready(self, *args, **kw):
+        _refuse("step_ready", "the play-through is not resumable yet: a step launch lasts as long as its longest search")
+
+    def check_errors(self):
+        """Raises if a launch since the last check saw an action outside the space or a tile id above 6.  Synchronises."""
+        _lib.check(self._L.pcgrl_smb_env_poll_error(self._handle()), "pcgrl_smb_env_poll_error")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._L.pcgrl_smb_env_destroy(self._h)
+            self._h = None
+            self._workspace = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _get(cfg, path, default=None):
+    cur = cfg
+    for part in path.split("."):
+        if cur is None:
+            return default
+        cur = cur.get(part, None) if isinstance(cur, dict) else getattr(cur, part, None)
+    return default if cur is None else cur
+
+
+def make_smb_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, sub_batches=1, reward_dtype=torch.float32):
+    """make_vec_env's branch for cfg.task.problem == "smb"; everything outside narrow / turtle stepping is refused by name."""
+    rep = _get(cfg, "representation")
+    if rep == "wide":
+        _refuse("the wide representation", "the reference's wide fails on a non-square map (wide_rep.py:42, IndexError)")
+    if _get(cfg, "controls") or _get(cfg, "task.controls"):
+        _refuse("controls", "controllable targets are only on the 2-D engine")
+    if _get(cfg, "static_prob") is not None or _get(cfg, "n_static_walls") is not None or _get(cfg, "static_tile_wrapper", False):
+        _refuse("static tiles", "the static-tile wrapper is only on the 2-D engine")
+    if _get(cfg, "act_window") is not None:
+        _refuse("act_window", "action patches are only on the 2-D engine")
+    if _get(cfg, "multiagent.n_agents", 0):
+        _refuse("multiagent.n_agents", "multi-agent turtle stepping is only built for binary and zelda")
+    if _get(cfg, "show_agents", False):
+        _refuse("show_agents", "it needs the multi-agent wrapper")
+    if (_get(cfg, "obs_format", "onehot") or "onehot") != "onehot":
+        _refuse('obs_format="codes"', "the tile-code observation is only on the engine's problems")
+    if int(sub_batches) > 1:
+        _refuse("sub_batches > 1", "an env is one wave already; there is no solver budget / step_ready for smb to overlap")
+    if _get(cfg, "n_aux_tiles", 0):
+        _refuse("n_aux_tiles", "auxiliary tiles are outside the accelerated path")
+    return SmbVecEnv(rep, tuple(_get(cfg, "task.map_shape")), num_envs, device=device, obs_window=_get(cfg, "task.obs_window"),
+                     weights=_get(cfg, "task.weights"), max_board_scans=_get(cfg, "max_board_scans", 3),
+                     change_percentage=_get(cfg, "change_percentage"), seeds=seeds, auto_reset=auto_reset,
+                     solver_power=_get(cfg, "task.solver_power", 10000), reward_dtype=reward_dtype)
+
+
+class SmbGymEnv:
+    """One Mario env with the reference's gym call shape on top of an SmbVecEnv of size 1: reset() -> (obs, {}), step(a) ->
+    (obs float32 [oh][ow][8], reward, done, truncated, info).  info holds the nine statistics only on a step that changed the
+    map (pcgrl_env.py:314-332), and always iterations, changes, max_iterations, max_changes."""
+
+    metadata = {"render.modes": []}
+
+    def __init__(self, cfg=None, vec=None, device="cuda:0", seed=None):
+        from .envs import Box, Discrete
+        self._vec = vec if vec is not None else make_smb_vec_env(cfg, 1, device=device, auto_reset=False,
+                                                                 seeds=None if seed is None else [seed],
+                                                                 reward_dtype=torch.float64)
+        assert self._vec.num_envs == 1 and not self._vec.auto_reset
+        v = self._vec
+        self.observation_space = Box(low=0, high=1, shape=v.obs_shape, dtype=np.float32)
+        self.action_space = Discrete(v.num_actions)
+        self.static_trgs = dict(v.spec.static_trgs)
+        self.metric_trgs = self.static_trgs
+        self.cond_bounds = dict(v.spec.cond_bounds)
+        self.ctrl_metrics = []
+        self.metric_weights = dict(v.weights)
+        self.metrics = {k: None for k in self.static_trgs}
+        self._rep_stats = None
+        self._changes = 0
+        self.render_mode = None
+
+    @property
+    def unwrapped(self):
+        return self
+
+    def seed(self, seed=None):
+        if seed is not None:
+            self._vec.seed([int(seed)])
+        return [seed]
+
+    def _stats_dict(self, row):
+        return {k: int(x) for k, x in zip(self._vec.stat_keys, row.tolist())}
+
+    def reset(self, *, seed=None, options=None):
+        if seed is not None:
+            self.seed(seed)
+        obs, _ = self._vec.reset()
+        self._rep_stats = self._stats_dict(self._vec.get_state().stats[0].cpu())
+        self.metrics = self._rep_stats
+        self._changes = 0
+        return obs[0].float().cpu().numpy(), {}
+
+    def step(self, action):
+        a = int(action)
+        if not 0 <= a < self.action_space.n:
+            raise IndexError(f"action {a} outside Discrete({self.action_space.n})")
+        obs, rew, done, _, info = self._vec.step(torch.tensor([a], dtype=torch.int32, device=self._vec.device))
+        self._rep_stats = self._stats_dict(info["stats"][0].cpu())
+        self.metrics = self._rep_stats
+        st = self._vec.get_state()
+        changes = int(st.changes[0])
+        out = dict(self._rep_stats) if changes != self._changes else {}
+        self._changes = changes
+        out.update(iterations=int(st.iteration[0]), changes=changes, max_iterations=int(self._vec.max_iterations),
+                   max_changes=self._vec.max_changes)
+        d = bool(done[0].item())
+        return obs[0].float().cpu().numpy(), float(rew[0].item()), d, d, out
+
+    def get_map(self):
+        return self._vec.get_state().grids[0].cpu().numpy()
+
+    def close(self):
+        self._vec.close()

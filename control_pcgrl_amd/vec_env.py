@@ -1062,7 +1062,11 @@ def make_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, su
     """Batched counterpart of control_pcgrl/rl/envs.py:make_env(cfg).  `cfg` is the reference's Config-like
     object (attributes or dict keys): task.problem, task.map_shape, task.obs_window, task.weights,
     representation, max_board_scans, change_percentage; obs_format ("onehot" default, or "codes": VecPcgrlEnv).
-    cfg.multiagent.n_agents != 0 (with or without cfg.show_agents): a multiagent.MultiAgentVecEnv."""
+    cfg.multiagent.n_agents != 0 (with or without cfg.show_agents): a multiagent.MultiAgentVecEnv.
+    cfg.task.problem == "smb" (narrow, turtle): a smb_env.SmbVecEnv."""
+    if _cfg_get(cfg, "task.problem") == "smb":  # an env class of its own: the engine does not know the problem
+        from .smb_env import make_smb_vec_env
+        return make_smb_vec_env(cfg, num_envs, device=device, seeds=seeds, auto_reset=auto_reset, sub_batches=sub_batches)
     unsupported = {
         "n_aux_tiles": _cfg_get(cfg, "n_aux_tiles", 0) or None,
     }
