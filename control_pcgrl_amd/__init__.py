@@ -9,6 +9,7 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   SmbEvaluator             Super Mario Bros levels: the nine statistics, the loss and the A* play-through of a batch of maps
                            in one launch (smb_spec() has the problem's tables)
   SmbVecEnv                cfg.task.problem == "smb": Mario envs stepped on the device (narrow, turtle), one launch per step
+  SmbReadyVecEnv           the same with cfg.task.solver_budget: a bounded, resumable play-through per launch and a status byte
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of
@@ -22,5 +23,6 @@ from .multiagent import MultiAgentGymEnv, MultiAgentVecEnv  # noqa: F401
 from .dist import EpisodeStatsReducer, shard_env_range  # noqa: F401
 from .smb import SmbEvaluator, smb_spec  # noqa: F401
 from .smb_env import SmbGymEnv, SmbVecEnv  # noqa: F401
+from .smb_ready import SmbReadyVecEnv  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

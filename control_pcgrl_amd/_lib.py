@@ -14,11 +14,11 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "codes/pcgrl_codes.hip", "reps3d/pcgrl_k_3d_turtle.hip", "reps3d/pcgrl_k_3d_wide.hip",
          "async3d/pcgrl_k_3d_async.hip", "paths/pcgrl_k_paths_binary.hip", "paths/pcgrl_k_paths_zelda.hip",
          "solutions/pcgrl_k_solutions.hip", "multiagent/pcgrl_k_ma_binary.hip", "multiagent/pcgrl_k_ma_zelda.hip",
-         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip"]
+         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip", "smb/pcgrl_k_smb_ready.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
-           "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h"]
+           "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -29,6 +29,7 @@ MULTIAGENT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_m
 MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_measures.h")
 SMB_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb.h")
 SMB_ENV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_env.h")
+SMB_READY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_ready.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -204,6 +205,15 @@ SMB_ENV_SYMBOLS = {
     "pcgrl_smb_env_poll_error": (C.c_int, [C.c_void_p]),
 }
 
+# include/pcgrl_amd_smb_ready.h: the same envs under a solver budget (a resumable play-through; works on an smb env handle)
+SMB_READY_SYMBOLS = {
+    "pcgrl_smb_ready_set_budget": (C.c_int, [C.c_void_p, C.c_int32]),
+    "pcgrl_smb_ready_get_budget": (C.c_int32, [C.c_void_p]),
+    "pcgrl_smb_ready_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+    "pcgrl_smb_ready_busy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_ready_park_bytes": (C.c_int64, [C.POINTER(PcgrlSmbEnvConfig)]),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -212,7 +222,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     out = out or LIB_PATH
     srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER, ASYNC3D_HEADER, PATHS_HEADER,
                                                        SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER, SMB_HEADER,
-                                                       SMB_ENV_HEADER]
+                                                       SMB_ENV_HEADER, SMB_READY_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -223,7 +233,8 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     hdr_time = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     hdr_time = max(hdr_time, os.path.getmtime(HEADER), os.path.getmtime(CODES_HEADER), os.path.getmtime(ASYNC3D_HEADER),
                    os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER),
-                   os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER), os.path.getmtime(SMB_ENV_HEADER))
+                   os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER), os.path.getmtime(SMB_ENV_HEADER),
+                   os.path.getmtime(SMB_READY_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -270,7 +281,8 @@ def lib():
         for name, (res, args) in (list(SYMBOLS.items()) + list(CODES_SYMBOLS.items()) + list(ASYNC3D_SYMBOLS.items())
                                   + list(PATHS_SYMBOLS.items()) + list(SOLUTIONS_SYMBOLS.items())
                                   + list(MULTIAGENT_SYMBOLS.items()) + list(MEASURES_SYMBOLS.items())
-                                  + list(SMB_SYMBOLS.items()) + list(SMB_ENV_SYMBOLS.items())):
+                                  + list(SMB_SYMBOLS.items()) + list(SMB_ENV_SYMBOLS.items())
+                                  + list(SMB_READY_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -37,6 +37,8 @@
 #include "../../include/pcgrl_amd_smb.h"
 #include "../../include/pcgrl_amd_smb_env.h"
 #include "smb/pcgrl_smb_env.h"
+#include "../../include/pcgrl_amd_smb_ready.h"
+#include "smb/pcgrl_smb_ready.h"  // the same envs under a solver budget
 
 using namespace pcgrl;
 
@@ -2184,6 +2186,8 @@ struct pcgrl_smb_env {
   int device = 0;
   SmbEnvArgs a = {};
   std::vector<void *> allocs;
+  int32_t budget = 0;       // include/pcgrl_amd_smb_ready.h: 0 = synchronous stepping
+  SmbPark *park = nullptr;  // [n], allocated by the first pcgrl_smb_ready_set_budget
 };
 
 static int smb_env_check(const char *who, const pcgrl_smb_env_config *c) {
@@ -2308,6 +2312,11 @@ int pcgrl_smb_env_reset(pcgrl_smb_env_handle h, const uint8_t *d_mask, const uin
   a.init_grids = d_init_grids;
   a.init_pos = d_init_pos;
   a.obs = d_obs;
+  if (h->budget > 0) {  // include/pcgrl_amd_smb_ready.h: the new levels' searches run under the budget
+    SmbReadyArgs ra = {a, h->park, h->budget, nullptr};
+    HIPCHK(launch_smb_ready_reset(ra, (hipStream_t)stream));
+    return PCGRL_OK;
+  }
   HIPCHK(launch_smb_env(SMB_ENV_RESET, a, (hipStream_t)stream));
   return PCGRL_OK;
 }
@@ -2316,6 +2325,9 @@ int pcgrl_smb_env_step(pcgrl_smb_env_handle h, const int32_t *d_actions, int32_t
                        double *d_reward64, uint8_t *d_done, int32_t *d_stats, void *stream) {
   if (!h || !d_actions) return fail(PCGRL_EINVAL, "pcgrl_smb_env_step: null handle or actions");
   if ((uintptr_t)d_obs & 15u) return fail(PCGRL_EINVAL, "pcgrl_smb_env_step: the observation must be 16-byte aligned");
+  if (h->budget > 0)
+    return fail(PCGRL_EINVAL, "pcgrl_smb_env_step: a solver budget is set and this call cannot say \"busy\": use "
+                              "pcgrl_smb_ready_step, or pcgrl_smb_ready_set_budget(h, 0)");
   ON_DEVICE(h->device);
   SmbEnvArgs a = h->a;
   a.actions = d_actions;
@@ -2390,6 +2402,75 @@ int pcgrl_smb_env_poll_error(pcgrl_smb_env_handle h) {
     if (flags & 1) return fail(PCGRL_EACTION, "an action was outside the action space (the reference raises IndexError)");
     if (flags & 2) return fail(PCGRL_EINVAL, "smb: a tile id above 6 was seen in init_grids (read as empty)");
   }
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------- Super Mario Bros environments under a solver budget
+// include/pcgrl_amd_smb_ready.h; kernels in smb/pcgrl_smb_ready.h.
+
+extern "C" {
+
+int64_t pcgrl_smb_ready_park_bytes(const pcgrl_smb_env_config *cfg) {
+  if (smb_env_check("pcgrl_smb_ready_park_bytes", cfg) != PCGRL_OK) return -1;
+  return (int64_t)sizeof(SmbPark);
+}
+
+int32_t pcgrl_smb_ready_get_budget(pcgrl_smb_env_handle h) { return h ? h->budget : -1; }
+
+int pcgrl_smb_ready_set_budget(pcgrl_smb_env_handle h, int32_t budget) {
+  const char *who = "pcgrl_smb_ready_set_budget";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (budget < 0) return fail(PCGRL_EINVAL, std::string(who) + ": the budget must be at least 0");
+  if (budget == h->budget) return PCGRL_OK;
+  ON_DEVICE(h->device);
+  const size_t n = (size_t)h->a.n;
+  if (budget == 0) {  // only when nothing is parked: the synchronous kernels know no park record
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<int32_t> mode(n);
+    HIPCHK(hipMemcpy2D(mode.data(), sizeof(int32_t), h->park, sizeof(SmbPark), sizeof(int32_t), n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++)
+      if (mode[i] != SMB_READY_IDLE)
+        return fail(PCGRL_EINVAL, std::string(who) + ": env " + std::to_string(i) + " is busy: step until no env is, or reset");
+  } else if (!h->park) {
+    void *p = nullptr;
+    HIPCHK(hipMalloc(&p, n * sizeof(SmbPark)));
+    h->allocs.push_back(p);
+    HIPCHK(hipMemset(p, 0, n * sizeof(SmbPark)));  // every env idle
+    HIPCHK(hipDeviceSynchronize());
+    h->park = (SmbPark *)p;
+  }
+  h->budget = budget;
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_ready_step(pcgrl_smb_env_handle h, const int32_t *d_actions, int32_t auto_reset, uint8_t *d_obs, float *d_reward,
+                         double *d_reward64, uint8_t *d_done, int32_t *d_stats, uint8_t *d_status, void *stream) {
+  if (!h || !d_actions || !d_status) return fail(PCGRL_EINVAL, "pcgrl_smb_ready_step: null handle, actions or status");
+  if ((uintptr_t)d_obs & 15u) return fail(PCGRL_EINVAL, "pcgrl_smb_ready_step: the observation must be 16-byte aligned");
+  if (h->budget < 1) return fail(PCGRL_EINVAL, "pcgrl_smb_ready_step: no solver budget is set (pcgrl_smb_ready_set_budget)");
+  ON_DEVICE(h->device);
+  SmbReadyArgs ra = {h->a, h->park, h->budget, d_status};
+  ra.e.actions = d_actions;
+  ra.e.auto_reset = auto_reset ? 1 : 0;
+  ra.e.obs = d_obs;
+  ra.e.reward = d_reward;
+  ra.e.reward64 = d_reward64;
+  ra.e.done = d_done;
+  ra.e.stats_out = d_stats;
+  HIPCHK(launch_smb_ready_step(ra, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_ready_busy(pcgrl_smb_env_handle h, uint8_t *d_busy, void *stream) {
+  if (!h || !d_busy) return fail(PCGRL_EINVAL, "pcgrl_smb_ready_busy: bad arguments");
+  ON_DEVICE(h->device);
+  if (!h->park) {  // no budget was ever set: nothing can be busy
+    HIPCHK(hipMemsetAsync(d_busy, 0, (size_t)h->a.n, (hipStream_t)stream));
+    return PCGRL_OK;
+  }
+  HIPCHK(launch_smb_ready_busy(h->park, h->a.n, d_busy, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

@@ -199,6 +199,7 @@ __device__ inline void smb_env_begin(SmbLds &L, const SmbEnvArgs &a, int env, Sm
   S.last_loss = smb_env_loss(a, S.stats);
 }
 
+#ifndef PCGRL_SMB_ENV_DEVICE_ONLY  // (smb/pcgrl_k_smb_ready.hip takes the device functions above without a second set of kernels)
 __global__ __launch_bounds__(64) void smb_env_reset_kernel(const SmbEnvArgs a) {
   __shared__ SmbLds L;
   const int env = blockIdx.x, lane = threadIdx.x;
@@ -394,6 +395,8 @@ __global__ __launch_bounds__(64) void smb_env_gather_kernel(const SmbEnvGather g
     if (g.last_stats) g.last_stats[(size_t)env * SMB_STATS + k] = S.last_stats[k];
   }
 }
+
+#endif  // PCGRL_SMB_ENV_DEVICE_ONLY
 
 #endif  // PCGRL_KERNEL_TU
 

@@ -186,10 +186,12 @@ class SmbVecEnv:
         return SimpleNamespace(ep_return=ret, length=length, stats=stats, count=count)
 
     def set_solver_budget(self, budget):
-        _refuse("a solver budget", "the play-through is not resumable yet: a step launch lasts as long as its longest search")
+        _refuse("a solver budget", "the play-through of this class is not resumable: a step launch lasts as long as its longest "
+                "search (smb_ready.SmbReadyVecEnv, cfg.task.solver_budget, has the resumable one)")
 
     def step_ready(self, *args, **kw):
-        _refuse("step_ready", "the play-through is not resumable yet: a step launch lasts as long as its longest search")
+        _refuse("step_ready", "the play-through of this class is not resumable: a step launch lasts as long as its longest "
+                "search (smb_ready.SmbReadyVecEnv, cfg.task.solver_budget, has the resumable one)")
 
     def check_errors(self):
         """Raises if a launch since the last check saw an action outside the space or a tile id above 6.  Synchronises."""
@@ -224,7 +226,8 @@ def _get(cfg, path, default=None):
 
 
 def make_smb_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, sub_batches=1, reward_dtype=torch.float32):
-    """make_vec_env's branch for cfg.task.problem == "smb"; everything outside narrow / turtle stepping is refused by name."""
+    """make_vec_env's branch for cfg.task.problem == "smb"; everything outside narrow / turtle stepping is refused by name.
+    A positive cfg.task.solver_budget gives smb_ready.SmbReadyVecEnv (asynchronous stepping), absent or 0 an SmbVecEnv."""
     rep = _get(cfg, "representation")
     if rep == "wide":
         _refuse("the wide representation", "the reference's wide fails on a non-square map (wide_rep.py:42, IndexError)")
@@ -241,13 +244,19 @@ def make_smb_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True
     if (_get(cfg, "obs_format", "onehot") or "onehot") != "onehot":
         _refuse('obs_format="codes"', "the tile-code observation is only on the engine's problems")
     if int(sub_batches) > 1:
-        _refuse("sub_batches > 1", "an env is one wave already; there is no solver budget / step_ready for smb to overlap")
+        _refuse("sub_batches > 1", "an env is one wave already, and the solver budget of smb_ready has nothing to overlap with")
     if _get(cfg, "n_aux_tiles", 0):
         _refuse("n_aux_tiles", "auxiliary tiles are outside the accelerated path")
-    return SmbVecEnv(rep, tuple(_get(cfg, "task.map_shape")), num_envs, device=device, obs_window=_get(cfg, "task.obs_window"),
-                     weights=_get(cfg, "task.weights"), max_board_scans=_get(cfg, "max_board_scans", 3),
-                     change_percentage=_get(cfg, "change_percentage"), seeds=seeds, auto_reset=auto_reset,
-                     solver_power=_get(cfg, "task.solver_power", 10000), reward_dtype=reward_dtype)
+    budget = _get(cfg, "task.solver_budget", 0)
+    if isinstance(budget, bool) or int(budget) != budget or int(budget) < 0:
+        raise ValueError(f"task.solver_budget must be a non-negative number of search iterations, got {budget!r}")
+    kw = dict(device=device, obs_window=_get(cfg, "task.obs_window"), weights=_get(cfg, "task.weights"),
+              max_board_scans=_get(cfg, "max_board_scans", 3), change_percentage=_get(cfg, "change_percentage"), seeds=seeds,
+              auto_reset=auto_reset, solver_power=_get(cfg, "task.solver_power", 10000), reward_dtype=reward_dtype)
+    if int(budget) > 0:
+        from .smb_ready import SmbReadyVecEnv
+        return SmbReadyVecEnv(rep, tuple(_get(cfg, "task.map_shape")), num_envs, solver_budget=int(budget), **kw)
+    return SmbVecEnv(rep, tuple(_get(cfg, "task.map_shape")), num_envs, **kw)
 
 
 class SmbGymEnv:
