@@ -14,11 +14,12 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "codes/pcgrl_codes.hip", "reps3d/pcgrl_k_3d_turtle.hip", "reps3d/pcgrl_k_3d_wide.hip",
          "async3d/pcgrl_k_3d_async.hip", "paths/pcgrl_k_paths_binary.hip", "paths/pcgrl_k_paths_zelda.hip",
          "solutions/pcgrl_k_solutions.hip", "multiagent/pcgrl_k_ma_binary.hip", "multiagent/pcgrl_k_ma_zelda.hip",
-         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip", "smb/pcgrl_k_smb_ready.hip"]
+         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip", "smb/pcgrl_k_smb_ready.hip",
+         "smb/pcgrl_k_smb_state.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
-           "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h"]
+           "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h", "smb/pcgrl_smb_state.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -30,6 +31,7 @@ MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mea
 SMB_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb.h")
 SMB_ENV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_env.h")
 SMB_READY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_ready.h")
+SMB_STATE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_state.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -214,6 +216,16 @@ SMB_READY_SYMBOLS = {
     "pcgrl_smb_ready_park_bytes": (C.c_int64, [C.POINTER(PcgrlSmbEnvConfig)]),
 }
 
+# include/pcgrl_amd_smb_state.h: checkpoint and restore of those envs (the image, the portable form, the RNG streams)
+SMB_STATE_SYMBOLS = {
+    "pcgrl_smb_state_bytes": (C.c_int64, [C.c_void_p]),
+    "pcgrl_smb_state_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_state_import": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4),
+    "pcgrl_smb_state_set": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
+    "pcgrl_smb_state_get_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_state_set_rng": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -222,7 +234,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     out = out or LIB_PATH
     srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER, ASYNC3D_HEADER, PATHS_HEADER,
                                                        SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER, SMB_HEADER,
-                                                       SMB_ENV_HEADER, SMB_READY_HEADER]
+                                                       SMB_ENV_HEADER, SMB_READY_HEADER, SMB_STATE_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -234,7 +246,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     hdr_time = max(hdr_time, os.path.getmtime(HEADER), os.path.getmtime(CODES_HEADER), os.path.getmtime(ASYNC3D_HEADER),
                    os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER),
                    os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER), os.path.getmtime(SMB_ENV_HEADER),
-                   os.path.getmtime(SMB_READY_HEADER))
+                   os.path.getmtime(SMB_READY_HEADER), os.path.getmtime(SMB_STATE_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -282,7 +294,7 @@ def lib():
                                   + list(PATHS_SYMBOLS.items()) + list(SOLUTIONS_SYMBOLS.items())
                                   + list(MULTIAGENT_SYMBOLS.items()) + list(MEASURES_SYMBOLS.items())
                                   + list(SMB_SYMBOLS.items()) + list(SMB_ENV_SYMBOLS.items())
-                                  + list(SMB_READY_SYMBOLS.items())):
+                                  + list(SMB_READY_SYMBOLS.items()) + list(SMB_STATE_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -39,6 +39,8 @@
 #include "smb/pcgrl_smb_env.h"
 #include "../../include/pcgrl_amd_smb_ready.h"
 #include "smb/pcgrl_smb_ready.h"  // the same envs under a solver budget
+#include "../../include/pcgrl_amd_smb_state.h"
+#include "smb/pcgrl_smb_state.h"  // their checkpoint and restore
 
 using namespace pcgrl;
 
@@ -2188,7 +2190,11 @@ struct pcgrl_smb_env {
   std::vector<void *> allocs;
   int32_t budget = 0;       // include/pcgrl_amd_smb_ready.h: 0 = synchronous stepping
   SmbPark *park = nullptr;  // [n], allocated by the first pcgrl_smb_ready_set_budget
+  uint8_t *state_hdr = nullptr;            // include/pcgrl_amd_smb_state.h: the image's 256-byte header, pinned and mapped
+  const uint8_t *state_hdr_dev = nullptr;  // the same block as the device sees it
 };
+
+static hipError_t smb_state_header_create(pcgrl_smb_env *e);
 
 static int smb_env_check(const char *who, const pcgrl_smb_env_config *c) {
   if (!c) return fail(PCGRL_EINVAL, std::string(who) + ": null config");
@@ -2271,6 +2277,7 @@ int pcgrl_smb_env_create(const pcgrl_smb_env_config *cfg, int32_t device, void *
   if (he == hipSuccess) he = alloc((void **)&a.jump, jt.size() * sizeof(JumpEntry));
   if (he == hipSuccess) he = alloc((void **)&a.err, 4 * sizeof(int32_t));
   if (he == hipSuccess) he = hipMemcpy((void *)a.jump, jt.data(), jt.size() * sizeof(JumpEntry), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = smb_state_header_create(e);
   if (he != hipSuccess) {
     pcgrl_smb_env_destroy(e);
     return fail(PCGRL_EHIP, std::string(who) + ": " + hipGetErrorString(he));
@@ -2285,6 +2292,7 @@ void pcgrl_smb_env_destroy(pcgrl_smb_env_handle h) {
   if (!h) return;
   DeviceGuard guard(h->device);
   for (void *p : h->allocs) (void)hipFree(p);
+  if (h->state_hdr) (void)hipHostFree(h->state_hdr);
   delete h;
 }
 
@@ -2400,7 +2408,9 @@ int pcgrl_smb_env_poll_error(pcgrl_smb_env_handle h) {
   if (flags) {
     HIPCHK(hipMemset(h->a.err, 0, sizeof(flags)));
     if (flags & 1) return fail(PCGRL_EACTION, "an action was outside the action space (the reference raises IndexError)");
-    if (flags & 2) return fail(PCGRL_EINVAL, "smb: a tile id above 6 was seen in init_grids (read as empty)");
+    if (flags & 2) return fail(PCGRL_EINVAL, "smb: a tile id above 6 was seen in init_grids or in the maps of pcgrl_smb_state_set (read as empty)");
+    if (flags & 4)
+      return fail(PCGRL_EINVAL, "smb: pcgrl_smb_state_import saw an index entry outside 0..n_envs-1 (the env was left as it was)");
   }
   return PCGRL_OK;
 }
@@ -2471,6 +2481,173 @@ int pcgrl_smb_ready_busy(pcgrl_smb_env_handle h, uint8_t *d_busy, void *stream) 
     return PCGRL_OK;
   }
   HIPCHK(launch_smb_ready_busy(h->park, h->a.n, d_busy, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------- Super Mario Bros environments: checkpoint and restore
+// include/pcgrl_amd_smb_state.h; kernels in smb/pcgrl_smb_state.h.
+
+struct SmbStateHeader {
+  uint64_t magic;        // "PCGRLSM1"
+  uint64_t fingerprint;  // FNV-1a over the create-time config fields, the library version string and the fields below
+  int32_t n_envs, map_stride, record_bytes, rng_bytes, mode_bytes, pad;
+  uint64_t total_bytes;
+};
+static constexpr uint64_t SMB_STATE_MAGIC = 0x314d534c52474350ull;  // "PCGRLSM1", little endian
+static_assert(sizeof(SmbStateHeader) <= SMB_STATE_HDR_BYTES, "state header section");
+
+static SmbStateHeader smb_state_header_of(const pcgrl_smb_env *e) {
+  SmbStateHeader hdr{};
+  hdr.magic = SMB_STATE_MAGIC;
+  hdr.n_envs = e->a.n;
+  hdr.map_stride = e->a.map_stride;
+  hdr.record_bytes = (int32_t)sizeof(SmbEnvState);
+  hdr.rng_bytes = SMB_STATE_RNG_WORDS * 8;
+  hdr.mode_bytes = 8;
+  hdr.total_bytes = (uint64_t)smb_state_layout(e->a.n, e->a.map_stride).total;
+  uint64_t x = 1469598103934665603ull;
+  auto mix = [&](const void *p, size_t n) {
+    for (size_t i = 0; i < n; i++) x = (x ^ ((const uint8_t *)p)[i]) * 1099511628211ull;
+  };
+  const pcgrl_smb_env_config &c = e->cfg;  // field by field: the struct's padding bytes are not part of the config
+#define MIX(f) mix(&c.f, sizeof(c.f))
+  MIX(h); MIX(w); MIX(representation); MIX(obs_window); MIX(max_iterations); MIX(max_changes); MIX(solver_power); MIX(n_envs);
+  MIX(has_trg); MIX(weight); MIX(trg_lo); MIX(trg_hi);
+#undef MIX
+  const char *v = pcgrl_version();
+  mix(v, strlen(v));
+  mix(&hdr.n_envs, sizeof(int32_t) * 6);
+  mix(&hdr.total_bytes, sizeof(hdr.total_bytes));
+  hdr.fingerprint = x;
+  return hdr;
+}
+
+// The header never changes after the create.  It lives in pinned, mapped host memory owned by the env: the export kernel reads
+// it from there, so a captured export keeps a pointer that stays valid.
+static hipError_t smb_state_header_create(pcgrl_smb_env *e) {
+  hipError_t he = hipHostMalloc((void **)&e->state_hdr, SMB_STATE_HDR_BYTES, hipHostMallocMapped);
+  if (he != hipSuccess) {
+    e->state_hdr = nullptr;
+    return he;
+  }
+  memset(e->state_hdr, 0, SMB_STATE_HDR_BYTES);
+  const SmbStateHeader hdr = smb_state_header_of(e);
+  memcpy(e->state_hdr, &hdr, sizeof(hdr));
+  return hipHostGetDevicePointer((void **)&e->state_hdr_dev, e->state_hdr, 0);
+}
+
+static SmbStateArgs smb_state_args_of(pcgrl_smb_env_handle h) {
+  SmbStateArgs sa = {};
+  sa.r.e = h->a;
+  sa.r.park = h->park;
+  sa.r.budget = h->budget;
+  return sa;
+}
+
+extern "C" {
+
+int64_t pcgrl_smb_state_bytes(pcgrl_smb_env_handle h) {
+  if (!h) {
+    (void)fail(PCGRL_EINVAL, "pcgrl_smb_state_bytes: null handle");
+    return -1;
+  }
+  return smb_state_layout(h->a.n, h->a.map_stride).total;
+}
+
+int pcgrl_smb_state_export(pcgrl_smb_env_handle h, uint8_t *d_buf, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_state_export: null handle");
+  if (!d_buf || ((uintptr_t)d_buf & 15u)) return fail(PCGRL_EINVAL, "pcgrl_smb_state_export: the image is null or not 16-byte aligned");
+  ON_DEVICE(h->device);
+  SmbStateArgs sa = smb_state_args_of(h);
+  sa.hdr = h->state_hdr_dev;
+  sa.image = d_buf;
+  HIPCHK(launch_smb_state(SMB_STATE_EXPORT, sa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_state_import(pcgrl_smb_env_handle h, const uint8_t *d_mask, const int32_t *d_index, const uint8_t *d_buf,
+                           void *stream) {
+  const char *who = "pcgrl_smb_state_import";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (!d_buf || ((uintptr_t)d_buf & 15u)) return fail(PCGRL_EINVAL, std::string(who) + ": the image is null or not 16-byte aligned");
+  ON_DEVICE(h->device);
+  const int32_t n = h->a.n;
+  const SmbStateLayout l = smb_state_layout(n, h->a.map_stride);
+  // the header is checked on the host before anything is overwritten: a small copy and one wait for `stream`.  Where the env
+  // has no budget the mask and the index come with it, and the modes once the header has said that the image has them.
+  const bool sync_env = h->budget == 0;
+  SmbStateHeader got{};
+  std::vector<int32_t> mode(sync_env ? (size_t)n * 2 : 0), index(sync_env && d_index ? n : 0);
+  std::vector<uint8_t> mask(sync_env && d_mask ? n : 0);
+  HIPCHK(hipMemcpyAsync(&got, d_buf, sizeof(got), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  if (sync_env) {
+    if (d_mask) HIPCHK(hipMemcpyAsync(mask.data(), d_mask, (size_t)n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (d_index) HIPCHK(hipMemcpyAsync(index.data(), d_index, (size_t)n * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  }
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  const SmbStateHeader want = smb_state_header_of(h);
+  if (got.magic != SMB_STATE_MAGIC) return fail(PCGRL_EINVAL, std::string(who) + ": not a pcgrl_smb_state_export image (bad magic)");
+  if (memcmp(&got, &want, sizeof(want)) != 0)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the image was exported by an env with another config, batch size, layout or "
+                                                 "library version");
+  if (sync_env) {
+    HIPCHK(hipMemcpyAsync(mode.data(), d_buf + l.mode, (size_t)n * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (nothing else is queued: the wait above has drained the stream)
+    int busy = 0;
+    for (int32_t i = 0; i < n; i++) {
+      if (d_mask && mask[i] == 0) continue;
+      const int32_t row = d_index ? index[i] : i;
+      if (row < 0 || row >= n) continue;  // overwrites nothing (the error bit)
+      busy += mode[(size_t)row * 2] != SMB_READY_IDLE ? 1 : 0;
+    }
+    if (busy)
+      return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": " + std::to_string(busy) + " of the rows to import are busy (a parked "
+                  "search of an env with a solver budget), which only pcgrl_smb_ready_step can finish: set a solver budget "
+                  "first, or mask them out");
+  }
+  SmbStateArgs sa = smb_state_args_of(h);
+  sa.r.e.mask = d_mask;
+  sa.index = d_index;
+  sa.image = (uint8_t *)d_buf;
+  HIPCHK(launch_smb_state(SMB_STATE_IMPORT, sa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_state_set(pcgrl_smb_env_handle h, const uint8_t *d_mask, const uint8_t *d_grids, const int32_t *d_pos,
+                        const int32_t *d_counters, const double *d_ep_return, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_state_set: null handle");
+  if (!d_grids) return fail(PCGRL_EINVAL, "pcgrl_smb_state_set: null maps");
+  ON_DEVICE(h->device);
+  SmbStateArgs sa = smb_state_args_of(h);
+  sa.r.e.mask = d_mask;
+  sa.r.e.init_grids = d_grids;
+  sa.pos = d_pos;
+  sa.counters = d_counters;
+  sa.ep_return = d_ep_return;
+  HIPCHK(launch_smb_state(SMB_STATE_SET, sa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_state_get_rng(pcgrl_smb_env_handle h, uint64_t *d_rng, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_state_get_rng: null handle");
+  if (!d_rng) return fail(PCGRL_EINVAL, "pcgrl_smb_state_get_rng: null output");
+  ON_DEVICE(h->device);
+  SmbStateArgs sa = smb_state_args_of(h);
+  sa.rng_out = d_rng;
+  HIPCHK(launch_smb_state(SMB_STATE_RNG, sa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_state_set_rng(pcgrl_smb_env_handle h, const uint8_t *d_mask, const uint64_t *d_rng, void *stream) {
+  if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_state_set_rng: null handle");
+  if (!d_rng) return fail(PCGRL_EINVAL, "pcgrl_smb_state_set_rng: null input");
+  ON_DEVICE(h->device);
+  SmbStateArgs sa = smb_state_args_of(h);
+  sa.r.e.mask = d_mask;
+  sa.rng_in = d_rng;
+  HIPCHK(launch_smb_state(SMB_STATE_RNG, sa, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

@@ -15,8 +15,11 @@
 //   resume    the committed map is loaded, a pending step's edit is replayed in LDS from the parked action, and smb_scan_level
 //             rebuilds the column masks and the five map statistics; nothing of the step in flight is stored before its search
 //             ends, so the committed state (map, SmbEnvState) is the one before the step.
-//   identity  a park record carries no copy of its map: an SMB env has no state import, a busy env takes no action, so only a
-//             reset can change a map under a parked search -- and a reset clears the selected envs' park records.
+//   identity  a park record carries no copy of its map.  A busy env takes no action, so three calls alone can change a map under
+//             a parked search, and each of them puts the park record right in the same launch: a reset and
+//             pcgrl_smb_state_set (smb/pcgrl_smb_state.h) abandon the search and start the new map's, and
+//             pcgrl_smb_state_import writes the record with the map -- idle, or the imported row's search "parked after 0
+//             iterations", the start of a search of the map it has just stored.  The envs outside their masks keep both.
 //   dirty     a search starts by writing nodes[0], heap[0] and a zeroed visited set; mode is written by every reset: neither a
 //             dirty workspace nor a dirty park record of a reset env matters.
 #pragma once
@@ -231,6 +234,7 @@ __device__ inline bool smb_ready_begin(SmbLds &L, const SmbReadyArgs &ra, int en
   return true;
 }
 
+#ifndef PCGRL_SMB_READY_DEVICE_ONLY  // (smb/pcgrl_k_smb_state.hip takes the device functions above without a second set of kernels)
 __global__ __launch_bounds__(64) void smb_ready_reset_kernel(const SmbReadyArgs ra) {
   __shared__ SmbLds L;
   const SmbEnvArgs &a = ra.e;
@@ -447,6 +451,8 @@ __global__ __launch_bounds__(256) void smb_ready_busy_kernel(const SmbPark *park
   const int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env < n) busy[env] = park[env].mode != SMB_READY_IDLE ? 1 : 0;
 }
+
+#endif  // PCGRL_SMB_READY_DEVICE_ONLY
 
 #endif  // PCGRL_KERNEL_TU
 

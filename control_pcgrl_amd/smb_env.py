@@ -185,6 +185,95 @@ class SmbVecEnv:
                                                           count.data_ptr(), self._stream()), "pcgrl_smb_env_get_last_episode")
         return SimpleNamespace(ep_return=ret, length=length, stats=stats, count=count)
 
+    # -- checkpoint / restore (include/pcgrl_amd_smb_state.h; envs/pcgrl_env.py:102-112 pickles the env) ----
+    def _dev(self, t, dtype, shape=None):
+        if t is None:
+            return None
+        t = torch.as_tensor(t, device=self.device).to(dtype).contiguous()
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
+        return t
+
+    @staticmethod
+    def _ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    @property
+    def state_bytes(self):
+        """bytes of export_state()'s image"""
+        return int(self._L.pcgrl_smb_state_bytes(self._handle()))
+
+    def export_state(self, out=None):
+        """uint8 [state_bytes]: the whole per-env state -- maps, records, both RNG streams, and under a solver budget each env's
+        mode and pending action (a parked search itself is not carried: it starts over after an import).  One launch, no sync,
+        capturable: a captured export writes `out` anew at every replay."""
+        if out is None:
+            out = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or out.numel() != self.state_bytes:
+            raise ValueError(f"out must be a contiguous uint8 tensor of {self.state_bytes} bytes on {self.device}")
+        _lib.check(self._L.pcgrl_smb_state_export(self._handle(), out.data_ptr(), self._stream()), "pcgrl_smb_state_export")
+        return out
+
+    def get_rng_state(self):
+        """uint64-as-int64 [N, 10]: both numpy-compatible PCG64 streams of every env (the layout of include/pcgrl_amd.h)."""
+        out = torch.empty((self.num_envs, 10), dtype=torch.int64, device=self.device)
+        _lib.check(self._L.pcgrl_smb_state_get_rng(self._handle(), out.data_ptr(), self._stream()), "pcgrl_smb_state_get_rng")
+        return out
+
+    def set_rng_state(self, rng, mask=None):
+        r = self._dev(rng, torch.int64, (self.num_envs, 10))
+        m = self._dev(mask, torch.uint8, (self.num_envs,))
+        _lib.check(self._L.pcgrl_smb_state_set_rng(self._handle(), self._ptr(m), r.data_ptr(), self._stream()),
+                   "pcgrl_smb_state_set_rng")
+
+    def set_state(self, grids, pos, counters, ep_return, mask=None):
+        """The inverse of get_state()'s first fields for the envs of `mask`: grids uint8 [N][H][W], pos int32 [N][2] (clamped to
+        the map), counters int32 [N][4] = iteration, changes, n_step, searches, ep_return float64 [N].  Statistics and last_loss
+        are recomputed from the maps; under a solver budget that may leave envs busy (env_busy()).  The last finished episode
+        and the RNG streams stay as they are."""
+        N = self.num_envs
+        g = self._dev(grids, torch.uint8, (N,) + self.map_shape)
+        p = self._dev(pos, torch.int32, (N, 2))
+        c = self._dev(counters, torch.int32, (N, 4))
+        r = self._dev(ep_return, torch.float64, (N,))
+        m = self._dev(mask, torch.uint8, (N,))
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.pcgrl_smb_state_set(self._handle(), self._ptr(m), g.data_ptr(), self._ptr(p), self._ptr(c),
+                                                   self._ptr(r), self._stream()), "pcgrl_smb_state_set")
+
+    def state_dict(self):
+        """Everything needed to continue bit-exactly later: `blob` is export_state()'s image; the portable fields (maps,
+        positions, counters = iteration, changes, n_step, searches, running returns, RNG streams) ride along."""
+        N, dev = self.num_envs, self.device
+        grids = torch.empty((N,) + self.map_shape, dtype=torch.uint8, device=dev)
+        pos = torch.empty((N, 2), dtype=torch.int32, device=dev)
+        counters = torch.empty((N, 4), dtype=torch.int32, device=dev)
+        ep_return = torch.empty(N, dtype=torch.float64, device=dev)
+        _lib.check(self._L.pcgrl_smb_env_get_state(self._handle(), grids.data_ptr(), pos.data_ptr(), counters.data_ptr(), None,
+                                                   None, ep_return.data_ptr(), None, self._stream()), "pcgrl_smb_env_get_state")
+        return {"grids": grids, "pos": pos, "counters": counters, "ep_return": ep_return, "rng": self.get_rng_state(),
+                "blob": self.export_state()}
+
+    def load_state_dict(self, sd, mask=None, index=None):
+        """With "blob": the image import -- env j of `mask` (all without one) continues as row index[j] (j without an index) of
+        the exporter; an image of another config or batch size is refused (ValueError), and so is a busy row for an env without
+        a solver budget (NotImplementedError); nothing is overwritten then.  Without "blob": set_state and set_rng_state."""
+        if "blob" in sd:
+            b = self._dev(sd["blob"], torch.uint8)
+            if b.dim() != 1 or b.numel() != self.state_bytes:
+                raise ValueError(f"state_dict from an env with another config or batch size: the image has {b.numel()} bytes, "
+                                 f"this env's has {self.state_bytes}")
+            m = self._dev(mask, torch.uint8, (self.num_envs,))
+            i = self._dev(index, torch.int32, (self.num_envs,))
+            with torch.cuda.device(self.device):
+                _lib.check(self._L.pcgrl_smb_state_import(self._handle(), self._ptr(m), self._ptr(i), b.data_ptr(),
+                                                          self._stream()), "pcgrl_smb_state_import")
+            return
+        if index is not None:
+            raise ValueError("index needs the image (\"blob\"): the portable fields are taken row for row")
+        self.set_state(sd["grids"], sd["pos"], sd["counters"], sd["ep_return"], mask=mask)
+        self.set_rng_state(sd["rng"], mask=mask)
+
     def set_solver_budget(self, budget):
         _refuse("a solver budget", "the play-through of this class is not resumable: a step launch lasts as long as its longest "
                 "search (smb_ready.SmbReadyVecEnv, cfg.task.solver_budget, has the resumable one)")
@@ -194,7 +283,8 @@ class SmbVecEnv:
                 "search (smb_ready.SmbReadyVecEnv, cfg.task.solver_budget, has the resumable one)")
 
     def check_errors(self):
-        """Raises if a launch since the last check saw an action outside the space or a tile id above 6.  Synchronises."""
+        """Raises if a launch since the last check saw an action outside the space, a tile id above 6 or an import index outside
+        the batch.  Synchronises."""
         _lib.check(self._L.pcgrl_smb_env_poll_error(self._handle()), "pcgrl_smb_env_poll_error")
 
     def close(self):

@@ -76,7 +76,8 @@ int pcgrl_smb_env_get_state(pcgrl_smb_env_handle h, uint8_t *d_grids, int32_t *d
 /* the last finished episode of every env: return, length, final statistics, and how many have finished */
 int pcgrl_smb_env_get_last_episode(pcgrl_smb_env_handle h, double *d_return, int32_t *d_length, int32_t *d_stats,
                                    int32_t *d_count, void *stream);
-/* synchronises; PCGRL_EACTION for an action outside the space, PCGRL_EINVAL for a tile id above 6 in d_init_grids */
+/* synchronises; PCGRL_EACTION for an action outside the space, PCGRL_EINVAL for a tile id above 6 in d_init_grids (or in the maps
+ * of pcgrl_amd_smb_state.h's set call) and for an import index outside the batch (pcgrl_amd_smb_state.h) */
 int pcgrl_smb_env_poll_error(pcgrl_smb_env_handle h);
 
 #ifdef __cplusplus

@@ -37,9 +37,10 @@
  * whose result was committed, the iteration counters count every iteration run, and the most one launch spent on an env never
  * exceeds the largest budget used.
  *
- * The park record carries the search loop's words, the env's mode and pending action and the visited set -- not the map: an SMB
- * env has no state import and a busy env takes no action, so only a reset can change a map under a parked search, and a reset
- * clears the park record.  Results never depend on stale parked state.
+ * The park record carries the search loop's words, the env's mode and pending action and the visited set -- not the map: a busy
+ * env takes no action, so only a reset or the set and import calls of pcgrl_amd_smb_state.h can change a map under a parked
+ * search, and each of them puts the selected envs' park records right in the same launch (a reset and the set call start the
+ * new map's search, an import writes idle or a search that starts over).  Results never depend on stale parked state.
  *
  * Every entry point checks its arguments before any HIP call (PCGRL_EINVAL: a null handle or argument, a misaligned observation, a
  * negative budget), enqueues on `stream` only, allocates nothing after the first pcgrl_smb_ready_set_budget and is HIP-graph
