@@ -9,6 +9,7 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   SmbEvaluator             Super Mario Bros levels: the nine statistics, the loss and the A* play-through of a batch of maps
                            in one launch (smb_spec() has the problem's tables)
   SmbVecEnv                cfg.task.problem == "smb": Mario envs stepped on the device (narrow, turtle), one launch per step
+                           -- or per K steps: rollout(), with given actions or actions drawn on the device
   SmbReadyVecEnv           the same with cfg.task.solver_budget: a bounded, resumable play-through per launch and a status byte
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device

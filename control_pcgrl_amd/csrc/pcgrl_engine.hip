@@ -41,6 +41,8 @@
 #include "smb/pcgrl_smb_ready.h"  // the same envs under a solver budget
 #include "../../include/pcgrl_amd_smb_state.h"
 #include "smb/pcgrl_smb_state.h"  // their checkpoint and restore
+#include "../../include/pcgrl_amd_smb_rollout.h"
+#include "smb/pcgrl_smb_rollout.h"  // K steps in one launch, device-drawn actions
 
 using namespace pcgrl;
 
@@ -2192,6 +2194,7 @@ struct pcgrl_smb_env {
   SmbPark *park = nullptr;  // [n], allocated by the first pcgrl_smb_ready_set_budget
   uint8_t *state_hdr = nullptr;            // include/pcgrl_amd_smb_state.h: the image's 256-byte header, pinned and mapped
   const uint8_t *state_hdr_dev = nullptr;  // the same block as the device sees it
+  SmbDrawState *draw = nullptr;            // include/pcgrl_amd_smb_rollout.h: the draw counter of the device-drawn actions
 };
 
 static hipError_t smb_state_header_create(pcgrl_smb_env *e);
@@ -2276,6 +2279,7 @@ int pcgrl_smb_env_create(const pcgrl_smb_env_config *cfg, int32_t device, void *
   if (he == hipSuccess) he = alloc((void **)&a.rng, n * sizeof(RngState));
   if (he == hipSuccess) he = alloc((void **)&a.jump, jt.size() * sizeof(JumpEntry));
   if (he == hipSuccess) he = alloc((void **)&a.err, 4 * sizeof(int32_t));
+  if (he == hipSuccess) he = alloc((void **)&e->draw, sizeof(SmbDrawState));
   if (he == hipSuccess) he = hipMemcpy((void *)a.jump, jt.data(), jt.size() * sizeof(JumpEntry), hipMemcpyHostToDevice);
   if (he == hipSuccess) he = smb_state_header_create(e);
   if (he != hipSuccess) {
@@ -2481,6 +2485,63 @@ int pcgrl_smb_ready_busy(pcgrl_smb_env_handle h, uint8_t *d_busy, void *stream) 
     return PCGRL_OK;
   }
   HIPCHK(launch_smb_ready_busy(h->park, h->a.n, d_busy, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------- Super Mario Bros environments: open-loop rollouts
+// include/pcgrl_amd_smb_rollout.h; kernels in smb/pcgrl_smb_rollout.h.
+
+extern "C" {
+
+int32_t pcgrl_smb_env_num_actions(pcgrl_smb_env_handle h) {
+  return h ? (h->a.rep == PCGRL_REP_NARROW ? SMB_TILES : 4 + SMB_TILES) : -1;
+}
+
+int pcgrl_smb_env_rollout(pcgrl_smb_env_handle h, const int32_t *d_actions, uint64_t seed, int32_t n_steps, int32_t auto_reset,
+                          uint8_t *d_obs, int32_t obs_mode, float *d_reward, double *d_reward64, uint8_t *d_done,
+                          int32_t *d_stats, int32_t *d_actions_out, int32_t *d_ep_count, double *d_ep_return_sum,
+                          int64_t *d_ep_length_sum, int64_t *d_ep_stats_sum, void *stream) {
+  const char *who = "pcgrl_smb_env_rollout";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (n_steps < 1) return fail(PCGRL_EINVAL, std::string(who) + ": n_steps must be at least 1");
+  if ((int64_t)n_steps * h->a.n > INT32_MAX)
+    return fail(PCGRL_EINVAL, std::string(who) + ": n_steps * n_envs must stay below 2^31");
+  if (obs_mode < 0 || obs_mode > 2) return fail(PCGRL_EINVAL, std::string(who) + ": obs_mode must be 0 (none), 1 (last) or 2 (all)");
+  if (obs_mode != 0 && (!d_obs || ((uintptr_t)d_obs & 15u)))
+    return fail(PCGRL_EINVAL, std::string(who) + ": the observation must be non-null and 16-byte aligned when obs_mode is not 0");
+  if (h->budget > 0)
+    return fail(PCGRL_EINVAL, std::string(who) + ": a solver budget is set and this call cannot say \"busy\": use "
+                                                 "pcgrl_smb_ready_step, or pcgrl_smb_ready_set_budget(h, 0)");
+  ON_DEVICE(h->device);
+  SmbRolloutArgs ra = {};
+  ra.e = h->a;
+  ra.e.actions = d_actions;
+  ra.e.auto_reset = auto_reset ? 1 : 0;
+  ra.e.obs = obs_mode != 0 ? d_obs : nullptr;
+  ra.e.reward = d_reward;
+  ra.e.reward64 = d_reward64;
+  ra.e.done = d_done;
+  ra.e.stats_out = d_stats;
+  ra.n_steps = n_steps;
+  ra.obs_mode = obs_mode;
+  ra.n_actions = pcgrl_smb_env_num_actions(h);
+  ra.seed = seed;
+  ra.draw = h->draw;
+  ra.actions_out = d_actions_out;
+  ra.ep_count = d_ep_count;
+  ra.ep_return_sum = d_ep_return_sum;
+  ra.ep_length_sum = d_ep_length_sum;
+  ra.ep_stats_sum = d_ep_stats_sum;
+  HIPCHK(launch_smb_env_rollout(ra, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_env_sample_actions(pcgrl_smb_env_handle h, int32_t *d_actions, uint64_t seed, void *stream) {
+  if (!h || !d_actions) return fail(PCGRL_EINVAL, "pcgrl_smb_env_sample_actions: null handle or actions");
+  ON_DEVICE(h->device);
+  HIPCHK(launch_smb_env_sample(d_actions, h->a.n, pcgrl_smb_env_num_actions(h), seed, h->draw, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

@@ -19,6 +19,29 @@ REPS = {"narrow": 0, "turtle": 1}
 MAX_OBS_WINDOW = 255  # Cropped.set_pad_size keeps the pad as int8: the reference fails above
 
 
+_OBS_MODES = {"none": 0, "last": 1, "all": 2}  # obs_mode of include/pcgrl_amd_smb_rollout.h
+_MASK64 = (1 << 64) - 1
+
+
+def sampled_actions(seed, first_draw, n_steps, num_envs, num_actions):
+    """The device-drawn actions on the host: int32 [n_steps, num_envs], row k the draw first_draw + k under `seed` -- what
+    SmbVecEnv.sample_actions and rollout(n_steps=...) take (include/pcgrl_amd_smb_rollout.h has the function)."""
+    def mix64(z):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+        return z ^ (z >> np.uint64(31))
+
+    with np.errstate(over="ignore"):
+        c = np.uint64(int(first_draw) & _MASK64) + np.arange(int(n_steps), dtype=np.uint64)
+        a = mix64(np.uint64(int(seed) & _MASK64) + c * np.uint64(0x9e3779b97f4a7c15))
+        i = np.arange(int(num_envs), dtype=np.uint64) * np.uint64(0xd1b54a32d192ed03) + np.uint64(0x8cb92ba72f3d8dd7)
+        r = mix64(a[:, None] ^ i[None, :])
+    # floor(r * num_actions / 2^64) from the two 32-bit halves: num_actions < 2^31, so nothing overflows
+    n = np.uint64(int(num_actions))
+    hi, lo = r >> np.uint64(32), r & np.uint64(0xFFFFFFFF)
+    return ((hi * n + ((lo * n) >> np.uint64(32))) >> np.uint64(32)).astype(np.int32)
+
+
 def _refuse(what, why):
     raise NotImplementedError(f"smb: {what} is not stepped on the device: {why}")
 
@@ -149,6 +172,80 @@ class SmbVecEnv:
         if rc:
             _lib.check(rc, "pcgrl_smb_env_step")
         return self._step_out
+
+    def sample_actions(self, seed=0, out=None):
+        """action_space.sample() for every env, drawn on the device: int32 [N], entry i of the handle's draw c under `seed` is
+        sampled_actions(seed, c, 1, N, num_actions)[0, i].  The draw counter lives on the device and advances by 1 in stream
+        order, so a captured call draws fresh actions at every replay."""
+        if out is None:
+            out = self.__dict__.get("_sampled")
+            if out is None:
+                out = self._sampled = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        elif (out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous()
+              or out.numel() != self.num_envs):
+            raise ValueError(f"out must be a contiguous int32 tensor of {self.num_envs} entries on {self.device}")
+        rc = self._L.pcgrl_smb_env_sample_actions(self._handle(), out.data_ptr(), int(seed) & _MASK64, self._stream())
+        if rc:
+            _lib.check(rc, "pcgrl_smb_env_sample_actions")
+        return out
+
+    def rollout(self, actions=None, n_steps=None, want_obs="last", seed=0):
+        """K steps of every env in ONE launch (include/pcgrl_amd_smb_rollout.h): bit for bit what K step()
+        calls give, but a launch lasts as long as its slowest env's own K steps instead of K times the batch's longest search.
+        For actions that do not depend on the observations.
+
+        actions int32 [K, N] (tensor, array or list), or None with n_steps=K: drawn on the device, the same actions as K times
+        [sample_actions(seed) -> step].  want_obs: "last" -> obs [N, ...] after the last step, "all" -> [K, N, ...] (row k what
+        step k would have returned), "none" -> None.  Returns a namespace: reward [K, N] (reward_dtype), done and truncated bool
+        [K, N], stats int32 [K, N, 9], obs, actions int32 [K, N] (the actions taken) and episodes -- count int32 [N],
+        return_sum float64 [N], length_sum int64 [N], stats_sum int64 [N, 9] over the episodes finished inside this launch.
+        The tensors are owned by the env, cached per (K, want_obs) and overwritten by the next call of that form; a second
+        call of a form allocates nothing and can be captured with torch.cuda.graph.  Honours auto_reset."""
+        if want_obs not in _OBS_MODES:
+            raise ValueError(f"want_obs must be one of {sorted(_OBS_MODES)}, got {want_obs!r}")
+        N = self.num_envs
+        if actions is None:
+            if n_steps is None:
+                raise ValueError("rollout needs actions [K, N], or n_steps for actions drawn on the device")
+            K, a_ptr = int(n_steps), None
+        else:
+            if not isinstance(actions, torch.Tensor):
+                actions = torch.as_tensor(np.asarray(actions))
+            if actions.dim() != 2 or actions.shape[1] != N:
+                raise ValueError(f"actions must be [K, {N}], got {tuple(actions.shape)}")
+            if n_steps is not None and int(n_steps) != actions.shape[0]:
+                raise ValueError(f"n_steps={n_steps} does not match actions of {actions.shape[0]} steps")
+            if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
+                actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
+            K, a_ptr = int(actions.shape[0]), actions.data_ptr()
+        if K < 1:
+            raise ValueError(f"a rollout takes at least one step, got {K}")
+        bufs = self.__dict__.setdefault("_rollouts", {})
+        b = bufs.get((K, want_obs))
+        if b is None:
+            dev = self.device
+            obs = {"none": None, "last": self._obs}[want_obs] if want_obs != "all" else torch.empty(
+                (K, N) + self.obs_shape, dtype=torch.uint8, device=dev)
+            done = torch.empty((K, N), dtype=torch.bool, device=dev)
+            b = SimpleNamespace(
+                reward=torch.empty((K, N), dtype=self._reward.dtype, device=dev), done=done, truncated=done,
+                stats=torch.empty((K, N, 9), dtype=torch.int32, device=dev), obs=obs,
+                actions=torch.empty((K, N), dtype=torch.int32, device=dev),
+                episodes=SimpleNamespace(count=torch.empty(N, dtype=torch.int32, device=dev),
+                                         return_sum=torch.empty(N, dtype=torch.float64, device=dev),
+                                         length_sum=torch.empty(N, dtype=torch.int64, device=dev),
+                                         stats_sum=torch.empty((N, 9), dtype=torch.int64, device=dev)))
+            bufs[(K, want_obs)] = b
+        r = b.reward.data_ptr()
+        ep = b.episodes
+        rc = self._L.pcgrl_smb_env_rollout(
+            self._handle(), a_ptr, int(seed) & _MASK64, K, 1 if self.auto_reset else 0,
+            b.obs.data_ptr() if b.obs is not None else None, _OBS_MODES[want_obs], r if self._r32 is not None else None,
+            r if self._r64 is not None else None, b.done.data_ptr(), b.stats.data_ptr(), b.actions.data_ptr(),
+            ep.count.data_ptr(), ep.return_sum.data_ptr(), ep.length_sum.data_ptr(), ep.stats_sum.data_ptr(), self._stream())
+        if rc:
+            _lib.check(rc, "pcgrl_smb_env_rollout")
+        return b
 
     def observe(self):
         _lib.check(self._L.pcgrl_smb_env_observe(self._handle(), self._obs.data_ptr(), self._stream()), "pcgrl_smb_env_observe")

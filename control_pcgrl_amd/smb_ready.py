@@ -51,6 +51,13 @@ class SmbReadyVecEnv(SmbVecEnv):
                                "step_ready(), or set_solver_budget(0) once no env is busy")
         return super().step(actions)
 
+    def rollout(self, *args, **kw):
+        if self.solver_budget > 0:
+            raise NotImplementedError("SmbReadyVecEnv.rollout: a solver budget is set and a rollout cannot say which envs are "
+                                      "busy: K steps in one launch run every search to its end.  Use step_ready(), or "
+                                      "set_solver_budget(0) once no env is busy")
+        return super().rollout(*args, **kw)
+
     def step_ready(self, actions):
         if actions.numel() != self.num_envs:
             raise ValueError(f"actions must be [{self.num_envs}], got {tuple(actions.shape)}")
