@@ -11,6 +11,7 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   SmbVecEnv                cfg.task.problem == "smb": Mario envs stepped on the device (narrow, turtle), one launch per step
                            -- or per K steps: rollout(), with given actions or actions drawn on the device
   SmbReadyVecEnv           the same with cfg.task.solver_budget: a bounded, resumable play-through per launch and a status byte
+                           (both take cfg.controls / controls=[...]: per-env targets, queue_targets, ctrl_obs, resampling)
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of

@@ -20,7 +20,7 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
            "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h", "smb/pcgrl_smb_state.h",
-           "smb/pcgrl_smb_rollout.h"]
+           "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -34,6 +34,7 @@ SMB_ENV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_
 SMB_READY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_ready.h")
 SMB_STATE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_state.h")
 SMB_ROLLOUT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_rollout.h")
+SMB_CTRL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_ctrl.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -236,6 +237,16 @@ SMB_ROLLOUT_SYMBOLS = {
     "pcgrl_smb_env_num_actions": (C.c_int32, [C.c_void_p]),
 }
 
+# include/pcgrl_amd_smb_ctrl.h: controllable generation for those envs (per-env targets, the control observation, resampling)
+SMB_CTRL_SYMBOLS = {
+    "pcgrl_smb_ctrl_attach": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4),
+    "pcgrl_smb_ctrl_count": (C.c_int32, [C.c_void_p]),
+    "pcgrl_smb_ctrl_queue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    "pcgrl_smb_ctrl_observe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_ctrl_set_resampling": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcgrl_smb_ctrl_get": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -245,7 +256,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER, ASYNC3D_HEADER, PATHS_HEADER,
                                                        SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER, SMB_HEADER,
                                                        SMB_ENV_HEADER, SMB_READY_HEADER, SMB_STATE_HEADER,
-                                                       SMB_ROLLOUT_HEADER]
+                                                       SMB_ROLLOUT_HEADER, SMB_CTRL_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -258,7 +269,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER),
                    os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER), os.path.getmtime(SMB_ENV_HEADER),
                    os.path.getmtime(SMB_READY_HEADER), os.path.getmtime(SMB_STATE_HEADER),
-                   os.path.getmtime(SMB_ROLLOUT_HEADER))
+                   os.path.getmtime(SMB_ROLLOUT_HEADER), os.path.getmtime(SMB_CTRL_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -307,7 +318,7 @@ def lib():
                                   + list(MULTIAGENT_SYMBOLS.items()) + list(MEASURES_SYMBOLS.items())
                                   + list(SMB_SYMBOLS.items()) + list(SMB_ENV_SYMBOLS.items())
                                   + list(SMB_READY_SYMBOLS.items()) + list(SMB_STATE_SYMBOLS.items())
-                                  + list(SMB_ROLLOUT_SYMBOLS.items())):
+                                  + list(SMB_ROLLOUT_SYMBOLS.items()) + list(SMB_CTRL_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -43,6 +45,8 @@
 #include "smb/pcgrl_smb_state.h"  // their checkpoint and restore
 #include "../../include/pcgrl_amd_smb_rollout.h"
 #include "smb/pcgrl_smb_rollout.h"  // K steps in one launch, device-drawn actions
+#include "../../include/pcgrl_amd_smb_ctrl.h"
+#include "smb/pcgrl_smb_ctrl.h"  // controllable generation: per-env targets
 
 using namespace pcgrl;
 
@@ -2195,6 +2199,8 @@ struct pcgrl_smb_env {
   uint8_t *state_hdr = nullptr;            // include/pcgrl_amd_smb_state.h: the image's 256-byte header, pinned and mapped
   const uint8_t *state_hdr_dev = nullptr;  // the same block as the device sees it
   SmbDrawState *draw = nullptr;            // include/pcgrl_amd_smb_rollout.h: the draw counter of the device-drawn actions
+  SmbCtrlCfg ctrl = {};                    // include/pcgrl_amd_smb_ctrl.h: n_ctrl 0 = not controllable (the host's copy)
+  bool touched = false;                    // a reset, a state set or an import has run: too late to attach controls
 };
 
 static hipError_t smb_state_header_create(pcgrl_smb_env *e);
@@ -2324,6 +2330,7 @@ int pcgrl_smb_env_reset(pcgrl_smb_env_handle h, const uint8_t *d_mask, const uin
   a.init_grids = d_init_grids;
   a.init_pos = d_init_pos;
   a.obs = d_obs;
+  h->touched = true;
   if (h->budget > 0) {  // include/pcgrl_amd_smb_ready.h: the new levels' searches run under the budget
     SmbReadyArgs ra = {a, h->park, h->budget, nullptr};
     HIPCHK(launch_smb_ready_reset(ra, (hipStream_t)stream));
@@ -2567,7 +2574,7 @@ static SmbStateHeader smb_state_header_of(const pcgrl_smb_env *e) {
   hdr.record_bytes = (int32_t)sizeof(SmbEnvState);
   hdr.rng_bytes = SMB_STATE_RNG_WORDS * 8;
   hdr.mode_bytes = 8;
-  hdr.total_bytes = (uint64_t)smb_state_layout(e->a.n, e->a.map_stride).total;
+  hdr.total_bytes = (uint64_t)smb_state_layout(e->a.n, e->a.map_stride, e->ctrl.n_ctrl > 0).total;
   uint64_t x = 1469598103934665603ull;
   auto mix = [&](const void *p, size_t n) {
     for (size_t i = 0; i < n; i++) x = (x ^ ((const uint8_t *)p)[i]) * 1099511628211ull;
@@ -2581,6 +2588,14 @@ static SmbStateHeader smb_state_header_of(const pcgrl_smb_env *e) {
   mix(v, strlen(v));
   mix(&hdr.n_envs, sizeof(int32_t) * 6);
   mix(&hdr.total_bytes, sizeof(hdr.total_bytes));
+  if (e->ctrl.n_ctrl > 0) {  // a controllable env: the control list and ranges (without controls the fingerprint is what it was)
+    const int32_t rec_bytes = (int32_t)sizeof(SmbCtrlRec);
+    mix("ctrl", 4);
+    mix(&rec_bytes, sizeof(rec_bytes));
+    mix(&e->ctrl.n_ctrl, sizeof(int32_t));
+    mix(e->ctrl.idx, sizeof(int32_t) * e->ctrl.n_ctrl);
+    mix(e->ctrl.range, sizeof(double) * e->ctrl.n_ctrl);
+  }
   hdr.fingerprint = x;
   return hdr;
 }
@@ -2614,7 +2629,7 @@ int64_t pcgrl_smb_state_bytes(pcgrl_smb_env_handle h) {
     (void)fail(PCGRL_EINVAL, "pcgrl_smb_state_bytes: null handle");
     return -1;
   }
-  return smb_state_layout(h->a.n, h->a.map_stride).total;
+  return smb_state_layout(h->a.n, h->a.map_stride, h->ctrl.n_ctrl > 0).total;
 }
 
 int pcgrl_smb_state_export(pcgrl_smb_env_handle h, uint8_t *d_buf, void *stream) {
@@ -2635,7 +2650,7 @@ int pcgrl_smb_state_import(pcgrl_smb_env_handle h, const uint8_t *d_mask, const 
   if (!d_buf || ((uintptr_t)d_buf & 15u)) return fail(PCGRL_EINVAL, std::string(who) + ": the image is null or not 16-byte aligned");
   ON_DEVICE(h->device);
   const int32_t n = h->a.n;
-  const SmbStateLayout l = smb_state_layout(n, h->a.map_stride);
+  const SmbStateLayout l = smb_state_layout(n, h->a.map_stride, h->ctrl.n_ctrl > 0);
   // the header is checked on the host before anything is overwritten: a small copy and one wait for `stream`.  Where the env
   // has no budget the mask and the index come with it, and the modes once the header has said that the image has them.
   const bool sync_env = h->budget == 0;
@@ -2651,8 +2666,9 @@ int pcgrl_smb_state_import(pcgrl_smb_env_handle h, const uint8_t *d_mask, const 
   const SmbStateHeader want = smb_state_header_of(h);
   if (got.magic != SMB_STATE_MAGIC) return fail(PCGRL_EINVAL, std::string(who) + ": not a pcgrl_smb_state_export image (bad magic)");
   if (memcmp(&got, &want, sizeof(want)) != 0)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the image was exported by an env with another config, batch size, layout or "
-                                                 "library version");
+    return fail(PCGRL_EINVAL, std::string(who) + ": the image was exported by an env with another config, batch size, layout, "
+                                                 "control list or library version");
+  h->touched = true;
   if (sync_env) {
     HIPCHK(hipMemcpyAsync(mode.data(), d_buf + l.mode, (size_t)n * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (nothing else is queued: the wait above has drained the stream)
@@ -2681,6 +2697,7 @@ int pcgrl_smb_state_set(pcgrl_smb_env_handle h, const uint8_t *d_mask, const uin
   if (!h) return fail(PCGRL_EINVAL, "pcgrl_smb_state_set: null handle");
   if (!d_grids) return fail(PCGRL_EINVAL, "pcgrl_smb_state_set: null maps");
   ON_DEVICE(h->device);
+  h->touched = true;
   SmbStateArgs sa = smb_state_args_of(h);
   sa.r.e.mask = d_mask;
   sa.r.e.init_grids = d_grids;
@@ -2709,6 +2726,154 @@ int pcgrl_smb_state_set_rng(pcgrl_smb_env_handle h, const uint8_t *d_mask, const
   sa.r.e.mask = d_mask;
   sa.rng_in = d_rng;
   HIPCHK(launch_smb_state(SMB_STATE_RNG, sa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ Super Mario Bros environments: controllable generation
+// include/pcgrl_amd_smb_ctrl.h; kernels in smb/pcgrl_smb_ctrl.h and, as the controllable instantiations, in every smb kernel file.
+
+extern "C" {
+
+int32_t pcgrl_smb_ctrl_count(pcgrl_smb_env_handle h) { return h ? h->ctrl.n_ctrl : -1; }
+
+int pcgrl_smb_ctrl_attach(pcgrl_smb_env_handle h, int32_t n_ctrl, const int32_t *ctrl_idx, const double *ctrl_range,
+                          const double *shown, float *d_ctrl_obs) {
+  const char *who = "pcgrl_smb_ctrl_attach";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (h->ctrl.n_ctrl > 0) return fail(PCGRL_EINVAL, std::string(who) + ": the env has controls already");
+  if (h->touched) return fail(PCGRL_EINVAL, std::string(who) + ": controls are attached before the first reset");
+  if (n_ctrl < 1 || n_ctrl > SMB_STATS || !ctrl_idx || !ctrl_range || !shown)
+    return fail(PCGRL_EINVAL, std::string(who) + ": n_ctrl must be in 1..9 and the index, range and value arrays non-null");
+  if ((uintptr_t)d_ctrl_obs & 7u) return fail(PCGRL_EINVAL, std::string(who) + ": the control observation must be 8-byte aligned");
+  uint32_t seen = 0;
+  for (int j = 0; j < n_ctrl; j++) {
+    if (ctrl_idx[j] < 0 || ctrl_idx[j] >= SMB_STATS)
+      return fail(PCGRL_EINVAL, std::string(who) + ": a control index is outside the nine statistics");
+    if ((seen >> ctrl_idx[j]) & 1u) return fail(PCGRL_EINVAL, std::string(who) + ": a statistic is listed twice");
+    seen |= 1u << ctrl_idx[j];
+    if (!(ctrl_range[j] > 0.0) || !std::isfinite(ctrl_range[j]) || !std::isfinite(shown[j]))
+      return fail(PCGRL_EINVAL, std::string(who) + ": ranges must be positive and finite, observed values finite");
+  }
+  ON_DEVICE(h->device);
+  SmbCtrlCfg cc = {};
+  cc.n_ctrl = n_ctrl;
+  SmbCtrlRec rec = {};
+  for (int k = 0; k < SMB_STATS; k++) {
+    rec.lo[k] = h->a.trg_lo[k];
+    rec.hi[k] = h->a.trg_hi[k];
+  }
+  for (int j = 0; j < n_ctrl; j++) {
+    cc.idx[j] = ctrl_idx[j];
+    cc.range[j] = ctrl_range[j];
+    rec.obs[j] = shown[j];
+  }
+  const std::vector<SmbCtrlRec> recs((size_t)h->a.n, rec);
+  void *d_cfg = nullptr, *d_rec = nullptr;
+  hipError_t he = hipMalloc(&d_cfg, sizeof(SmbCtrlCfg));
+  if (he == hipSuccess) {
+    h->allocs.push_back(d_cfg);
+    he = hipMalloc(&d_rec, recs.size() * sizeof(SmbCtrlRec));
+  }
+  if (he == hipSuccess) {
+    h->allocs.push_back(d_rec);
+    he = hipMemcpy(d_cfg, &cc, sizeof(cc), hipMemcpyHostToDevice);
+  }
+  if (he == hipSuccess) he = hipMemcpy(d_rec, recs.data(), recs.size() * sizeof(SmbCtrlRec), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipDeviceSynchronize();
+  if (he != hipSuccess) return fail(PCGRL_EHIP, std::string(who) + ": " + hipGetErrorString(he));
+  h->ctrl = cc;
+  h->a.ctrl.cfg = (const SmbCtrlCfg *)d_cfg;
+  h->a.ctrl.rec = (SmbCtrlRec *)d_rec;
+  h->a.ctrl.obs = d_ctrl_obs;
+  const SmbStateHeader hdr = smb_state_header_of(h);  // the image gains the control section: a new size and fingerprint
+  memcpy(h->state_hdr, &hdr, sizeof(hdr));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_ctrl_queue(pcgrl_smb_env_handle h, const uint8_t *d_mask, int32_t n_named, const int32_t *named,
+                         const double *d_lo, const double *d_hi, const double *d_shown, void *stream) {
+  const char *who = "pcgrl_smb_ctrl_queue";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (h->ctrl.n_ctrl < 1) return fail(PCGRL_EINVAL, std::string(who) + ": the env has no controls (pcgrl_smb_ctrl_attach)");
+  if (n_named < 1 || n_named > h->ctrl.n_ctrl || !named || !d_lo || !d_hi || !d_shown)
+    return fail(PCGRL_EINVAL, std::string(who) + ": between 1 and n_ctrl named controls, and non-null lo, hi and observed values");
+  SmbCtrlQueueArgs qa = {};
+  uint32_t seen = 0;
+  for (int i = 0; i < n_named; i++) {
+    if (named[i] < 0 || named[i] >= h->ctrl.n_ctrl)
+      return fail(PCGRL_EINVAL, std::string(who) + ": a named control is outside 0..n_ctrl-1");
+    if ((seen >> named[i]) & 1u) return fail(PCGRL_EINVAL, std::string(who) + ": a control is named twice");
+    seen |= 1u << named[i];
+    qa.named[i] = named[i];
+  }
+  ON_DEVICE(h->device);
+  qa.n = h->a.n;
+  qa.n_named = n_named;
+  qa.rec = h->a.ctrl.rec;
+  qa.mask = d_mask;
+  qa.lo = d_lo;
+  qa.hi = d_hi;
+  qa.obs = d_shown;
+  HIPCHK(launch_smb_ctrl_queue(qa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_ctrl_observe(pcgrl_smb_env_handle h, float *d_ctrl_obs, void *stream) {
+  const char *who = "pcgrl_smb_ctrl_observe";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (h->ctrl.n_ctrl < 1) return fail(PCGRL_EINVAL, std::string(who) + ": the env has no controls (pcgrl_smb_ctrl_attach)");
+  float *out = d_ctrl_obs ? d_ctrl_obs : h->a.ctrl.obs;
+  if (!out) return fail(PCGRL_EINVAL, std::string(who) + ": no output and no attached control observation");
+  ON_DEVICE(h->device);
+  SmbCtrlObserveArgs oa = {};
+  oa.n = h->a.n;
+  oa.c = h->a.ctrl;
+  oa.c.obs = out;
+  oa.stats = (const int32_t *)h->a.st;
+  oa.stats_stride = (int64_t)sizeof(SmbEnvState);
+  oa.stats_offset = (int64_t)offsetof(SmbEnvState, stats);
+  HIPCHK(launch_smb_ctrl_observe(oa, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_ctrl_set_resampling(pcgrl_smb_env_handle h, int32_t enable, uint64_t seed, const double *lo, const double *hi,
+                                  void *stream) {
+  const char *who = "pcgrl_smb_ctrl_set_resampling";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (h->ctrl.n_ctrl < 1) return fail(PCGRL_EINVAL, std::string(who) + ": the env has no controls (pcgrl_smb_ctrl_attach)");
+  if (enable && (!lo || !hi)) return fail(PCGRL_EINVAL, std::string(who) + ": resampling needs lo and hi per control");
+  SmbCtrlResampleArgs ra = {};
+  for (int j = 0; j < h->ctrl.n_ctrl; j++) {
+    ra.lo[j] = lo ? lo[j] : 0.0;
+    ra.hi[j] = hi ? hi[j] : 0.0;
+    if (!std::isfinite(ra.lo[j]) || !std::isfinite(ra.hi[j]))
+      return fail(PCGRL_EINVAL, std::string(who) + ": the bounds must be finite");
+  }
+  ON_DEVICE(h->device);
+  ra.cfg = (SmbCtrlCfg *)h->a.ctrl.cfg;
+  ra.enable = enable ? 1 : 0;
+  ra.n_ctrl = h->ctrl.n_ctrl;
+  ra.seed = seed;
+  HIPCHK(launch_smb_ctrl_resample(ra, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_smb_ctrl_get(pcgrl_smb_env_handle h, double *d_active, double *d_shown, double *d_queued, int32_t *d_flags,
+                       void *stream) {
+  const char *who = "pcgrl_smb_ctrl_get";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  if (h->ctrl.n_ctrl < 1) return fail(PCGRL_EINVAL, std::string(who) + ": the env has no controls (pcgrl_smb_ctrl_attach)");
+  ON_DEVICE(h->device);
+  SmbCtrlGetArgs ga = {};
+  ga.n = h->a.n;
+  ga.rec = h->a.ctrl.rec;
+  ga.active = d_active;
+  ga.shown = d_shown;
+  ga.queued = d_queued;
+  ga.flags = d_flags;
+  HIPCHK(launch_smb_ctrl_get(ga, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

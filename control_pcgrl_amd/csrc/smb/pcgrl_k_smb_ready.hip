@@ -9,13 +9,15 @@ namespace pcgrl {
 
 hipError_t launch_smb_ready_step(const SmbReadyArgs &a, hipStream_t s) {
   if (a.e.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(smb_ready_step_kernel, dim3(a.e.n), dim3(64), 0, s, a);
+  if (a.e.ctrl.rec) hipLaunchKernelGGL(smb_ready_step_kernel<true>, dim3(a.e.n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(smb_ready_step_kernel<false>, dim3(a.e.n), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_smb_ready_reset(const SmbReadyArgs &a, hipStream_t s) {
   if (a.e.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(smb_ready_reset_kernel, dim3(a.e.n), dim3(64), 0, s, a);
+  if (a.e.ctrl.rec) hipLaunchKernelGGL(smb_ready_reset_kernel<true>, dim3(a.e.n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(smb_ready_reset_kernel<false>, dim3(a.e.n), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

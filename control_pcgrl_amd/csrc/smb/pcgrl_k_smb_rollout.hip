@@ -9,7 +9,8 @@ namespace pcgrl {
 
 hipError_t launch_smb_env_rollout(const SmbRolloutArgs &a, hipStream_t s) {
   if (a.e.n <= 0 || a.n_steps <= 0) return hipSuccess;
-  hipLaunchKernelGGL(smb_env_rollout_kernel, dim3(a.e.n), dim3(64), 0, s, a);
+  if (a.e.ctrl.rec) hipLaunchKernelGGL(smb_env_rollout_kernel<true>, dim3(a.e.n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(smb_env_rollout_kernel<false>, dim3(a.e.n), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

@@ -14,7 +14,10 @@ hipError_t launch_smb_state(SmbStateKernel k, const SmbStateArgs &a, hipStream_t
   switch (k) {
     case SMB_STATE_EXPORT: hipLaunchKernelGGL(smb_state_export_kernel, grid, block, 0, s, a); break;
     case SMB_STATE_IMPORT: hipLaunchKernelGGL(smb_state_import_kernel, grid, block, 0, s, a); break;
-    case SMB_STATE_SET: hipLaunchKernelGGL(smb_state_set_kernel, grid, block, 0, s, a); break;
+    case SMB_STATE_SET:
+      if (a.r.e.ctrl.rec) hipLaunchKernelGGL(smb_state_set_kernel<true>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(smb_state_set_kernel<false>, grid, block, 0, s, a);
+      break;
     case SMB_STATE_RNG: hipLaunchKernelGGL(smb_state_rng_kernel, grid, block, 0, s, a); break;
   }
   return hipGetLastError();

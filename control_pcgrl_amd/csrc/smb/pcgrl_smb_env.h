@@ -25,6 +25,7 @@
 
 #include "../pcgrl_common.h"
 #include "pcgrl_smb.h"
+#include "pcgrl_smb_ctrl.h"
 
 namespace pcgrl {
 
@@ -67,6 +68,7 @@ struct SmbEnvArgs {
   int32_t *stats_out;
   int32_t has_trg[SMB_STATS];
   double weight[SMB_STATS], trg_lo[SMB_STATS], trg_hi[SMB_STATS];
+  SmbCtrlArgs ctrl;  // a controllable handle (smb/pcgrl_smb_ctrl.h): the per-env targets replace trg_lo / trg_hi
 };
 
 // what pcgrl_smb_env_get_state / get_last_episode gather; any pointer may be null
@@ -106,6 +108,13 @@ __device__ inline double smb_env_loss(const SmbEnvArgs &a, const int32_t *stats)
     loss += -d * a.weight[k];
   }
   return loss;
+}
+// the same against the targets a controllable launch holds in LDS (SmbCtrlNone: the static ones above)
+__device__ __forceinline__ double smb_env_loss(const SmbEnvArgs &a, const int32_t *stats, const SmbCtrlNone &) {
+  return smb_env_loss(a, stats);
+}
+__device__ __forceinline__ double smb_env_loss(const SmbEnvArgs &a, const int32_t *stats, const SmbCtrlLds &C) {
+  return smb_ctrl_loss(C, a.has_trg, a.weight, stats);
 }
 
 // envs/pcgrl_env.py:158-188: the next episode's map into L.map and its start into pos; lane 0 stores the advanced streams
@@ -182,7 +191,8 @@ __device__ inline void smb_env_store_map(const SmbLds &L, const SmbEnvArgs &a, i
 }
 
 // a fresh episode on the map in L.map: the search, the counters, last_loss (every lane holds the same S)
-__device__ inline void smb_env_begin(SmbLds &L, const SmbEnvArgs &a, int env, SmbEnvState &S, const int *pos) {
+template <class CtrlLds>
+__device__ inline void smb_env_begin(SmbLds &L, const SmbEnvArgs &a, int env, SmbEnvState &S, const int *pos, CtrlLds &C) {
   uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
   SmbPlayOut out = {nullptr, nullptr, 0, 0};
   SmbResult r;
@@ -196,17 +206,21 @@ __device__ inline void smb_env_begin(SmbLds &L, const SmbEnvArgs &a, int env, Sm
   S.iters_total += r.it1 + r.it2;
   S.iters_max = max(S.iters_max, r.it1 + r.it2);
   S.ep_return = 0.0;
-  S.last_loss = smb_env_loss(a, S.stats);
+  smb_ctrl_take(C, a.ctrl, env, threadIdx.x & 63);  // the queued or resampled targets, before the new level's loss
+  S.last_loss = smb_env_loss(a, S.stats, C);
 }
 
 #ifndef PCGRL_SMB_ENV_DEVICE_ONLY  // (smb/pcgrl_k_smb_ready.hip takes the device functions above without a second set of kernels)
+template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_env_reset_kernel(const SmbEnvArgs a) {
   __shared__ SmbLds L;
+  __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
   const int H = a.h, W = a.w, cells = H * W;
   const bool active = !a.mask || a.mask[env] != 0;
   SmbEnvState *P = a.st + env;
+  smb_ctrl_load(C, a.ctrl, env, lane);
   SmbEnvState S;  // what smb_env_begin reads and writes; the last finished episode stays where it is
   S.searches = P->searches;
   S.iters_total = P->iters_total;
@@ -216,6 +230,7 @@ __global__ __launch_bounds__(64) void smb_env_reset_kernel(const SmbEnvArgs a) {
     smb_env_load_map(L, a, env, lane);
     __syncthreads();
     smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
+    if constexpr (CTRL) smb_ctrl_write_obs(C, a.ctrl, env, lane, P->stats);
     return;
   }
   for (int i = cells + lane; i < a.map_stride; i += 64) L.map[i] = 0;  // the padding of the stored row
@@ -242,7 +257,8 @@ __global__ __launch_bounds__(64) void smb_env_reset_kernel(const SmbEnvArgs a) {
   __syncthreads();
   smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
   smb_env_store_map(L, a, env, lane);
-  smb_env_begin(L, a, env, S, pos);
+  smb_env_begin(L, a, env, S, pos, C);
+  smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
   if (lane == 0) {
     P->pos[0] = S.pos[0];
     P->pos[1] = S.pos[1];
@@ -266,13 +282,16 @@ __global__ __launch_bounds__(64) void smb_env_observe_kernel(const SmbEnvArgs a)
   smb_env_write_obs(L, a, env, lane, a.st[env].pos[0], a.st[env].pos[1]);
 }
 
+template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_env_step_kernel(const SmbEnvArgs a) {
   __shared__ SmbLds L;
+  __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
   const int H = a.h, W = a.w, cells = H * W;
   smb_env_load_map(L, a, env, lane);
   SmbEnvState S = a.st[env];
+  smb_ctrl_load(C, a.ctrl, env, lane);
   const int act = a.actions[env];
   const int n_act = a.rep == PCGRL_REP_NARROW ? SMB_TILES : 4 + SMB_TILES;
   __syncthreads();
@@ -286,6 +305,7 @@ __global__ __launch_bounds__(64) void smb_env_step_kernel(const SmbEnvArgs a) {
         for (int k = 0; k < SMB_STATS; k++) a.stats_out[(size_t)env * SMB_STATS + k] = S.stats[k];
     }
     smb_env_write_obs(L, a, env, lane, S.pos[0], S.pos[1]);
+    smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
     return;
   }
   // the representation's update (narrow_rep.py:89-102, turtle_rep.py:87-107)
@@ -340,7 +360,7 @@ __global__ __launch_bounds__(64) void smb_env_step_kernel(const SmbEnvArgs a) {
       S.iters_max = max(S.iters_max, r.it1 + r.it2);
     }
   }
-  const double loss = smb_env_loss(a, S.stats);
+  const double loss = smb_env_loss(a, S.stats, C);
   const double reward = loss - S.last_loss;  // control_wrappers.py:227-229
   S.last_loss = loss;
   S.ep_return += reward;
@@ -366,8 +386,9 @@ __global__ __launch_bounds__(64) void smb_env_step_kernel(const SmbEnvArgs a) {
     __syncthreads();
     smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
     smb_env_store_map(L, a, env, lane);
-    smb_env_begin(L, a, env, S, pos);
+    smb_env_begin(L, a, env, S, pos, C);
   }
+  smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);  // the new episode's, where the step began one
   if (lane == 0) a.st[env] = S;
 }
 

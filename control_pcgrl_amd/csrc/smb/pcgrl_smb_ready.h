@@ -215,7 +215,9 @@ __device__ __forceinline__ void smb_ready_count(SmbEnvState &S, int spent) {
 // A fresh episode on the map in L.map (stored already, its observation written): the counters, then the search with what the
 // launch has left.  True when it finished (statistics and last_loss are set, as smb_env_begin sets them); false leaves the env
 // with pending statistics.  Every lane holds the same S.
-__device__ inline bool smb_ready_begin(SmbLds &L, const SmbReadyArgs &ra, int env, SmbEnvState &S, const int *pos, int &left) {
+template <class CtrlLds>
+__device__ inline bool smb_ready_begin(SmbLds &L, const SmbReadyArgs &ra, int env, SmbEnvState &S, const int *pos, int &left,
+                                       CtrlLds &C) {
   const SmbEnvArgs &a = ra.e;
   uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
   SmbResult r;
@@ -224,25 +226,30 @@ __device__ inline bool smb_ready_begin(SmbLds &L, const SmbReadyArgs &ra, int en
   S.pos[1] = pos[1];
   S.n_step = S.iteration = S.changes = S.ep_len = 0;
   S.ep_return = 0.0;
+  // the queued or resampled targets are committed by the launch that brings the new level, whenever its search ends
+  smb_ctrl_take(C, a.ctrl, env, threadIdx.x & 63);
   if (!smb_play_budgeted(L, a.h, a.w, a.power, (uint2 *)slot, (uint32_t *)(slot + smb_nodes_per_pass(a.power) * 8), ra.park + env,
                          false, left, r))
     return false;
 #pragma unroll
   for (int k = 0; k < SMB_STATS; k++) S.stats[k] = r.stats[k];
   S.searches++;
-  S.last_loss = smb_env_loss(a, S.stats);
+  S.last_loss = smb_env_loss(a, S.stats, C);
   return true;
 }
 
 #ifndef PCGRL_SMB_READY_DEVICE_ONLY  // (smb/pcgrl_k_smb_state.hip takes the device functions above without a second set of kernels)
+template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_ready_reset_kernel(const SmbReadyArgs ra) {
   __shared__ SmbLds L;
+  __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const SmbEnvArgs &a = ra.e;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
   const int H = a.h, W = a.w, cells = H * W;
   const bool active = !a.mask || a.mask[env] != 0;
   SmbEnvState *Q = a.st + env;
+  smb_ctrl_load(C, a.ctrl, env, lane);
   SmbEnvState S;  // what smb_ready_begin reads and writes; the last finished episode stays where it is
   S.searches = Q->searches;
   S.iters_total = Q->iters_total;
@@ -252,6 +259,7 @@ __global__ __launch_bounds__(64) void smb_ready_reset_kernel(const SmbReadyArgs 
     smb_env_load_map(L, a, env, lane);
     __syncthreads();
     smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
+    if constexpr (CTRL) smb_ctrl_write_obs(C, a.ctrl, env, lane, Q->stats);
     return;
   }
   for (int i = cells + lane; i < a.map_stride; i += 64) L.map[i] = 0;  // the padding of the stored row
@@ -279,8 +287,12 @@ __global__ __launch_bounds__(64) void smb_ready_reset_kernel(const SmbReadyArgs 
   smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
   smb_env_store_map(L, a, env, lane);
   int left = ra.budget;
-  const bool finished = smb_ready_begin(L, ra, env, S, pos, left);  // whatever was in flight is abandoned: a fresh search
+  const bool finished = smb_ready_begin(L, ra, env, S, pos, left, C);  // whatever was in flight is abandoned: a fresh search
   smb_ready_count(S, ra.budget - left);
+  if constexpr (CTRL) {  // (pending statistics: the old level's value until the search is over)
+    if (finished) smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
+    else smb_ctrl_write_obs(C, a.ctrl, env, lane, Q->stats);
+  }
   if (lane == 0) {
     ra.park[env].mode = finished ? SMB_READY_IDLE : SMB_READY_PENDING_STATS;
     Q->pos[0] = S.pos[0];
@@ -298,14 +310,17 @@ __global__ __launch_bounds__(64) void smb_ready_reset_kernel(const SmbReadyArgs 
   }
 }
 
+template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_ready_step_kernel(const SmbReadyArgs ra) {
   __shared__ SmbLds L;
+  __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const SmbEnvArgs &a = ra.e;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
   const int H = a.h, W = a.w, cells = H * W;
   smb_env_load_map(L, a, env, lane);
   SmbEnvState S = a.st[env];
+  smb_ctrl_load(C, a.ctrl, env, lane);
   SmbPark *P = ra.park + env;
   const int mode = P->mode;
   int left = ra.budget;
@@ -323,8 +338,9 @@ __global__ __launch_bounds__(64) void smb_ready_step_kernel(const SmbReadyArgs r
 #pragma unroll
       for (int k = 0; k < SMB_STATS; k++) S.stats[k] = r.stats[k];
       S.searches++;
-      S.last_loss = smb_env_loss(a, S.stats);
+      S.last_loss = smb_env_loss(a, S.stats, C);  // the targets the launch that brought the level committed
     }
+    smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
     if (lane == 0) {
       if (finished) P->mode = SMB_READY_IDLE;
       a.st[env] = S;
@@ -346,6 +362,7 @@ __global__ __launch_bounds__(64) void smb_ready_step_kernel(const SmbReadyArgs r
       ra.status[env] = (uint8_t)PCGRL_ENV_EMITTED;
     }
     smb_env_write_obs(L, a, env, lane, S.pos[0], S.pos[1]);
+    smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
     return;
   }
   // the representation's update, on the LDS copy alone: the step is committed only when its search is over
@@ -410,7 +427,7 @@ __global__ __launch_bounds__(64) void smb_ready_step_kernel(const SmbReadyArgs r
     }
     smb_env_store_map(L, a, env, lane);
   }
-  const double loss = smb_env_loss(a, S.stats);
+  const double loss = smb_env_loss(a, S.stats, C);
   const double reward = loss - S.last_loss;
   S.last_loss = loss;
   S.ep_return += reward;
@@ -437,9 +454,10 @@ __global__ __launch_bounds__(64) void smb_ready_step_kernel(const SmbReadyArgs r
     __syncthreads();
     smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
     smb_env_store_map(L, a, env, lane);
-    if (!smb_ready_begin(L, ra, env, S, pos, left)) next_mode = SMB_READY_PENDING_STATS;
+    if (!smb_ready_begin(L, ra, env, S, pos, left, C)) next_mode = SMB_READY_PENDING_STATS;
   }
   smb_ready_count(S, ra.budget - left);
+  smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
   if (lane == 0) {
     if (next_mode != mode) P->mode = next_mode;
     a.st[env] = S;

@@ -80,14 +80,17 @@ __global__ __launch_bounds__(256) void smb_env_sample_kernel(int32_t *out, int32
   if (i < n) out[i] = smb_sampled_action(seed, c_sh, i, n_actions);
 }
 
+template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_env_rollout_kernel(const SmbRolloutArgs ra) {
   __shared__ SmbLds L;
+  __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const SmbEnvArgs &a = ra.e;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
   const int H = a.h, W = a.w, cells = H * W, N = a.n, K = ra.n_steps;
   smb_env_load_map(L, a, env, lane);
   SmbEnvState S = a.st[env];
+  smb_ctrl_load(C, a.ctrl, env, lane);
   uint64_t c0 = 0;
   if (!a.actions) {
     unsigned long long c = 0;
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(64) void smb_env_rollout_kernel(const SmbRolloutArg
         S.iters_max = max(S.iters_max, r.it1 + r.it2);
       }
     }
-    const double loss = smb_env_loss(a, S.stats);
+    const double loss = smb_env_loss(a, S.stats, C);
     const double reward = loss - S.last_loss;  // control_wrappers.py:227-229
     S.last_loss = loss;
     S.ep_return += reward;
@@ -206,9 +209,10 @@ __global__ __launch_bounds__(64) void smb_env_rollout_kernel(const SmbRolloutArg
       smb_env_draw(L, a, env, lane, pos);
       __syncthreads();
       if (want_obs) smb_env_write_obs(L, a, obs_row, lane, pos[0], pos[1]);
-      smb_env_begin(L, a, env, S, pos);
+      smb_env_begin(L, a, env, S, pos, C);
     }
   }
+  smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);  // the control observation after the last step
   if (dirty) smb_env_store_map(L, a, env, lane);
   if (lane == 0) a.st[env] = S;
 }

@@ -16,6 +16,10 @@
 //             the stepping kernels resume it as they resume any parked search, and their code is what it was.
 //   set       the map, position, counters and return from the caller; the nine statistics and last_loss by the level's
 //             evaluation, under the budget where one is set (unfinished -> pending statistics, as a reset leaves them).
+//   controls  the image of a controllable env (smb/pcgrl_smb_ctrl.h) has a fifth section, the SmbCtrlRec records [n][448], on the
+//             next 16-byte boundary: active and queued targets, the queue set and the flag word with the draw counter.  The
+//             resampling switch, seed and bounds are run-time state and are not in the image.  Without controls there is no
+//             such section and the image is what it was.
 //   errors    err[0] bit 1: a tile id above 6 in pcgrl_smb_state_set's maps (read as empty); bit 2: an index entry outside
 //             0..n-1 (the env is left as it was).
 #pragma once
@@ -32,15 +36,17 @@ static_assert(sizeof(RngState) == 64, "RngState layout");
 
 // where the sections of an image of n envs start
 struct SmbStateLayout {
-  int64_t maps, st, rng, mode, total;
+  int64_t maps, st, rng, mode, total, ctrl;
 };
-__host__ __device__ inline SmbStateLayout smb_state_layout(int n, int map_stride) {
+__host__ __device__ inline SmbStateLayout smb_state_layout(int n, int map_stride, bool ctrl = false) {
   SmbStateLayout l;
   l.maps = SMB_STATE_HDR_BYTES;
   l.st = l.maps + (int64_t)n * map_stride;
   l.rng = l.st + (int64_t)n * (int64_t)sizeof(SmbEnvState);
   l.mode = l.rng + (int64_t)n * SMB_STATE_RNG_WORDS * 8;
   l.total = l.mode + (int64_t)n * 8;
+  l.ctrl = (l.total + 15) & ~(int64_t)15;
+  if (ctrl) l.total = l.ctrl + (int64_t)n * (int64_t)sizeof(SmbCtrlRec);
   return l;
 }
 
@@ -66,7 +72,7 @@ __global__ __launch_bounds__(64) void smb_state_export_kernel(const SmbStateArgs
   const SmbEnvArgs &a = sa.r.e;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
-  const SmbStateLayout l = smb_state_layout(a.n, a.map_stride);
+  const SmbStateLayout l = smb_state_layout(a.n, a.map_stride, a.ctrl.rec != nullptr);
   if (env == 0 && lane < SMB_STATE_HDR_BYTES / 16) ((uint4 *)sa.image)[lane] = ((const uint4 *)sa.hdr)[lane];
   const uint4 *src = (const uint4 *)(a.maps + (size_t)env * a.map_stride);
   uint4 *dst = (uint4 *)(sa.image + l.maps + (size_t)env * a.map_stride);
@@ -92,6 +98,8 @@ __global__ __launch_bounds__(64) void smb_state_export_kernel(const SmbStateArgs
     ((uint64_t *)(sa.image + l.rng))[(size_t)env * SMB_STATE_RNG_WORDS + lane] = lane < 8 ? r[lane] : 0ull;
   }
   if (lane == 0) ((int2 *)(sa.image + l.mode))[env] = make_int2(mode, action);
+  if (a.ctrl.rec && lane < (int)(sizeof(SmbCtrlRec) / 16))
+    ((uint4 *)(sa.image + l.ctrl))[(size_t)env * (sizeof(SmbCtrlRec) / 16) + lane] = ((const uint4 *)(a.ctrl.rec + env))[lane];
 }
 
 __global__ __launch_bounds__(64) void smb_state_import_kernel(const SmbStateArgs sa) {
@@ -104,12 +112,14 @@ __global__ __launch_bounds__(64) void smb_state_import_kernel(const SmbStateArgs
     if (lane == 0) atomicOr(a.err, 4);
     return;
   }
-  const SmbStateLayout l = smb_state_layout(a.n, a.map_stride);
+  const SmbStateLayout l = smb_state_layout(a.n, a.map_stride, a.ctrl.rec != nullptr);
   const uint4 *src = (const uint4 *)(sa.image + l.maps + (size_t)row * a.map_stride);
   uint4 *dst = (uint4 *)(a.maps + (size_t)env * a.map_stride);
   for (int i = lane; i < a.map_stride / 16; i += 64) dst[i] = src[i];
   if (lane < 9) ((uint4 *)(a.st + env))[lane] = ((const uint4 *)(sa.image + l.st))[(size_t)row * 9 + lane];
   if (lane < 8) ((uint64_t *)(a.rng + env))[lane] = ((const uint64_t *)(sa.image + l.rng))[(size_t)row * SMB_STATE_RNG_WORDS + lane];
+  if (a.ctrl.rec && lane < (int)(sizeof(SmbCtrlRec) / 16))
+    ((uint4 *)(a.ctrl.rec + env))[lane] = ((const uint4 *)(sa.image + l.ctrl))[(size_t)row * (sizeof(SmbCtrlRec) / 16) + lane];
   if (!sa.r.park) return;  // (the host has refused a busy row for an env without a budget)
   int2 m = ((const int2 *)(sa.image + l.mode))[row];
   if (m.x != SMB_READY_PENDING_STEP && m.x != SMB_READY_PENDING_STATS) m = make_int2(SMB_READY_IDLE, 0);
@@ -129,12 +139,15 @@ __global__ __launch_bounds__(64) void smb_state_import_kernel(const SmbStateArgs
   }
 }
 
+template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_state_set_kernel(const SmbStateArgs sa) {
   __shared__ SmbLds L;
+  __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const SmbEnvArgs &a = sa.r.e;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
   if (a.mask && a.mask[env] == 0) return;
+  smb_ctrl_load(C, a.ctrl, env, lane);  // the active targets: setting a state is no reset and takes nothing from the queue
   const int H = a.h, W = a.w, cells = H * W;
   for (int i = cells + lane; i < a.map_stride; i += 64) L.map[i] = 0;  // the padding of the stored row
   const uint8_t *g = a.init_grids + (size_t)env * cells;
@@ -181,6 +194,7 @@ __global__ __launch_bounds__(64) void smb_state_set_kernel(const SmbStateArgs sa
     spent = r.it1 + r.it2;
     if (lane == 0 && sa.r.park) sa.r.park[env].mode = SMB_READY_IDLE;
   }
+  if constexpr (CTRL) smb_ctrl_write_obs(C, a.ctrl, env, lane, finished ? r.stats : Q->stats);
   if (lane != 0) return;
   Q->pos[0] = p0;
   Q->pos[1] = p1;
@@ -195,7 +209,7 @@ __global__ __launch_bounds__(64) void smb_state_set_kernel(const SmbStateArgs sa
   if (finished) {  // pending statistics keep the old ones until the search is over
 #pragma unroll
     for (int k = 0; k < SMB_STATS; k++) Q->stats[k] = r.stats[k];
-    Q->last_loss = smb_env_loss(a, r.stats);
+    Q->last_loss = smb_env_loss(a, r.stats, C);
   }
 }
 

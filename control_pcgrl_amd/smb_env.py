@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .problems import target_interval
 from .smb import MAX_H, MAX_SOLVER_POWER, MAX_W, MIN_H, SMB_TILES, smb_config, smb_spec
 
 REPS = {"narrow": 0, "turtle": 1}
@@ -52,11 +53,15 @@ class SmbVecEnv:
 
     step(actions) -> (obs uint8 [N][oh][ow][8], reward [N], done bool [N], truncated (= done), info); info["stats"] is int32
     [N][9] (stat_keys order): the statistics after the step, of the finished episode where the step ended one.  With auto_reset a
-    finished env draws its next episode inside the same launch and the observation returned is that episode's first."""
+    finished env draws its next episode inside the same launch and the observation returned is that episode's first.
+
+    controls=[...] (statistics' names) makes the env controllable (include/pcgrl_amd_smb_ctrl.h): per-env
+    targets on the device, queue_targets / set_target_resampling, info["ctrl_obs"] float32 [N][2K] = per control (target / range,
+    statistic / range) from reset / step / step_ready, and float64 rewards."""
 
     def __init__(self, representation, map_shape=(16, 116), num_envs=1, device="cuda:0", obs_window=None, weights=None,
                  max_board_scans=3, change_percentage=None, seeds=None, auto_reset=True, solver_power=10000,
-                 reward_dtype=torch.float32):
+                 reward_dtype=torch.float32, controls=None):
         self._h = None
         self._L = _lib.lib()
         if representation == "wide":
@@ -84,6 +89,14 @@ class SmbVecEnv:
         self.num_envs, self.auto_reset, self.solver_power = int(num_envs), bool(auto_reset), int(solver_power)
         self.spec = smb_spec(map_shape)
         self.stat_keys = list(self.spec.stat_keys)
+        self.controls = list(controls) if controls else []
+        for k in self.controls:
+            if k not in self.stat_keys:
+                raise ValueError(f"'{k}' is not an smb statistic ({self.stat_keys})")
+        if len(set(self.controls)) != len(self.controls):
+            raise ValueError(f"a control metric is listed twice: {self.controls}")
+        if self.controls:
+            reward_dtype = torch.float64  # as make_vec_env: float targets make rewards that float32 would round
         self.num_actions = len(SMB_TILES) if representation == "narrow" else 4 + len(SMB_TILES)
         self.obs_shape = obs_window + (len(SMB_TILES) + 1,)
         self.max_iterations = H * W * int(max_board_scans) + 1  # pcgrl_env.py:241
@@ -119,6 +132,19 @@ class SmbVecEnv:
         self._r32 = self._reward.data_ptr() if reward_dtype == torch.float32 else None
         self._r64 = self._reward.data_ptr() if reward_dtype == torch.float64 else None
         self._step_out = (self._obs, self._reward, self._done, self._done, {"stats": self._stats})
+        self._ctrl_obs, self._reset_info = None, {}
+        if self.controls:
+            K = len(self.controls)
+            idx = np.array([self.stat_keys.index(k) for k in self.controls], dtype=np.int32)
+            self.ctrl_ranges = {k: abs(self.spec.cond_bounds[k][1] - self.spec.cond_bounds[k][0]) for k in self.controls}
+            rng = np.array([self.ctrl_ranges[k] for k in self.controls], dtype=np.float64)
+            shown = np.array([self._shown(self.spec.static_trgs[k]) for k in self.controls], dtype=np.float64)
+            self._ctrl_obs = torch.zeros((N, 2 * K), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(self._L.pcgrl_smb_ctrl_attach(h, K, idx.ctypes.data, rng.ctypes.data, shown.ctypes.data,
+                                                         self._ctrl_obs.data_ptr()), "pcgrl_smb_ctrl_attach")
+            self._reset_info = {"ctrl_obs": self._ctrl_obs}
+            self._step_out[4]["ctrl_obs"] = self._ctrl_obs
         if seeds is not None:
             self.seed(seeds)
 
@@ -160,7 +186,95 @@ class SmbVecEnv:
                                                    g.data_ptr() if g is not None else None,
                                                    p.data_ptr() if p is not None else None, self._obs.data_ptr(), self._stream()),
                        "pcgrl_smb_env_reset")
-        return self._obs, {}
+        return self._obs, self._reset_info
+
+    # -- controllable generation (control_wrappers.py:27-121; include/pcgrl_amd_smb_ctrl.h) -------------------------------------
+    @property
+    def ctrl_obs(self):
+        """float32 [N][2K], written by the last reset / step / step_ready / rollout / set_state (None without controls)"""
+        return self._ctrl_obs
+
+    @staticmethod
+    def _shown(trg):
+        # control_wrappers.py:203-204: a tuple target shows the midpoint of the raw tuple, not of its zero-loss interval
+        return (trg[0] + trg[1]) / 2 if isinstance(trg, tuple) else float(trg)
+
+    def _need_controls(self):
+        if not self.controls:
+            raise ValueError("this env was built without `controls`")
+
+    def queue_targets(self, trgs, mask=None):
+        """ControlWrapper.set_trgs: `trgs` = {metric: scalar | (lo, hi) | tensor [N]}; the targets take effect at each env's
+        next reset (explicit or automatic) and replace those of the named metrics only; a second call before that reset
+        replaces the first (control_wrappers.py:167-178).  A tuple means the reference's min |arange(lo, hi) - value|, so its
+        lo must be a whole number (the statistics are integers; hi need not be)."""
+        self._need_controls()
+        if not trgs:
+            raise ValueError("queue_targets needs at least one metric")
+        N, dev = self.num_envs, self.device
+        named, cols = [], []
+        for k, v in trgs.items():
+            if k not in self.controls:
+                raise ValueError(f"'{k}' is not a control metric of this env ({self.controls})")
+            named.append(self.controls.index(k))
+            if isinstance(v, tuple):
+                if len(v) != 2 or float(v[0]) != int(v[0]):
+                    raise ValueError(f"a tuple target is (lo, hi) with a whole-number lo, got {v!r}")
+                a, b = target_interval((float(v[0]), float(v[1])))
+                lo, hi, sh = (torch.full((N,), x, dtype=torch.float64, device=dev) for x in (a, b, self._shown(v)))
+            else:
+                t = torch.as_tensor(v, dtype=torch.float64, device=dev)
+                if t.dim() > 1 or (t.dim() == 1 and t.numel() != N):
+                    raise ValueError(f"a tensor target must be [{N}], got {tuple(t.shape)}")
+                lo = hi = sh = t.expand(N) if t.dim() == 0 else t
+            cols.append((lo, hi, sh))
+        lo, hi, sh = (torch.stack([c[i] for c in cols], dim=1).contiguous() for i in range(3))
+        m = None if mask is None else self._dev(mask, torch.uint8, (N,))
+        nm = np.array(named, dtype=np.int32)
+        _lib.check(self._L.pcgrl_smb_ctrl_queue(self._handle(), self._ptr(m), len(named), nm.ctypes.data, lo.data_ptr(),
+                                                hi.data_ptr(), sh.data_ptr(), self._stream()), "pcgrl_smb_ctrl_queue")
+
+    def sample_uniform_targets(self, generator=None, mask=None):
+        """UniformNoiseyTargets.set_rand_trgs (control_wrappers.py:453-460): each control target ~ U(cond_bounds), queued."""
+        self._need_controls()
+        trgs = {}
+        for k in self.controls:
+            lb, ub = self.spec.cond_bounds[k]
+            u = torch.rand(self.num_envs, generator=generator, device=self.device, dtype=torch.float64)
+            trgs[k] = u * (ub - lb) + lb
+        self.queue_targets(trgs, mask=mask)
+        return trgs
+
+    def set_target_resampling(self, enable=True, seed=0):
+        """UniformNoiseyTargets on the device: from each env's next reset on -- explicit or automatic, also inside a captured
+        HIP graph -- every control target is drawn ~ U(cond_bounds) from the env's own counter-based stream and replaces whatever
+        was queued.  The draw is the engine's trg_resampled (csrc/pcgrl_kernels2d.h) with the env's draw counter."""
+        self._need_controls()
+        lo = np.array([self.spec.cond_bounds[k][0] for k in self.controls], dtype=np.float64)
+        hi = np.array([self.spec.cond_bounds[k][1] for k in self.controls], dtype=np.float64)
+        _lib.check(self._L.pcgrl_smb_ctrl_set_resampling(self._handle(), 1 if enable else 0, int(seed) & _MASK64, lo.ctypes.data,
+                                                         hi.ctypes.data, self._stream()), "pcgrl_smb_ctrl_set_resampling")
+
+    def get_targets(self):
+        """The per-env control records: lo, hi float64 [N][9] (the active zero-loss intervals, stat_keys order), shown float64
+        [N][K] (the value the control observation shows per control), queued float64 [N][K][3] = lo, hi, shown, queued_set
+        int32 [N] (bit j: the queue names control j), pending bool [N], draws int32 [N] (the env's draw counter)."""
+        self._need_controls()
+        N, dev, K = self.num_envs, self.device, len(self.controls)
+        active = torch.empty((N, 9, 2), dtype=torch.float64, device=dev)
+        shown = torch.empty((N, 9), dtype=torch.float64, device=dev)
+        queued = torch.empty((N, 9, 3), dtype=torch.float64, device=dev)
+        flags = torch.empty((N, 2), dtype=torch.int32, device=dev)
+        _lib.check(self._L.pcgrl_smb_ctrl_get(self._handle(), active.data_ptr(), shown.data_ptr(), queued.data_ptr(),
+                                              flags.data_ptr(), self._stream()), "pcgrl_smb_ctrl_get")
+        return SimpleNamespace(lo=active[:, :, 0], hi=active[:, :, 1], shown=shown[:, :K], queued=queued[:, :K],
+                               queued_set=flags[:, 1], pending=(flags[:, 0] & 1) != 0, draws=flags[:, 0] >> 1)
+
+    def observe_controls(self):
+        """the control observation of the committed state, into ctrl_obs"""
+        self._need_controls()
+        _lib.check(self._L.pcgrl_smb_ctrl_observe(self._handle(), None, self._stream()), "pcgrl_smb_ctrl_observe")
+        return self._ctrl_obs
 
     def step(self, actions):
         if actions.numel() != self.num_envs:
@@ -197,7 +311,8 @@ class SmbVecEnv:
         actions int32 [K, N] (tensor, array or list), or None with n_steps=K: drawn on the device, the same actions as K times
         [sample_actions(seed) -> step].  want_obs: "last" -> obs [N, ...] after the last step, "all" -> [K, N, ...] (row k what
         step k would have returned), "none" -> None.  Returns a namespace: reward [K, N] (reward_dtype), done and truncated bool
-        [K, N], stats int32 [K, N, 9], obs, actions int32 [K, N] (the actions taken) and episodes -- count int32 [N],
+        [K, N], stats int32 [K, N, 9], obs, ctrl_obs (with controls: float32 [N, 2K] after the last step, else None), actions
+        int32 [K, N] (the actions taken) and episodes -- count int32 [N],
         return_sum float64 [N], length_sum int64 [N], stats_sum int64 [N, 9] over the episodes finished inside this launch.
         The tensors are owned by the env, cached per (K, want_obs) and overwritten by the next call of that form; a second
         call of a form allocates nothing and can be captured with torch.cuda.graph.  Honours auto_reset."""
@@ -229,7 +344,7 @@ class SmbVecEnv:
             done = torch.empty((K, N), dtype=torch.bool, device=dev)
             b = SimpleNamespace(
                 reward=torch.empty((K, N), dtype=self._reward.dtype, device=dev), done=done, truncated=done,
-                stats=torch.empty((K, N, 9), dtype=torch.int32, device=dev), obs=obs,
+                stats=torch.empty((K, N, 9), dtype=torch.int32, device=dev), obs=obs, ctrl_obs=self._ctrl_obs,
                 actions=torch.empty((K, N), dtype=torch.int32, device=dev),
                 episodes=SimpleNamespace(count=torch.empty(N, dtype=torch.int32, device=dev),
                                          return_sum=torch.empty(N, dtype=torch.float64, device=dev),
@@ -302,7 +417,8 @@ class SmbVecEnv:
 
     def export_state(self, out=None):
         """uint8 [state_bytes]: the whole per-env state -- maps, records, both RNG streams, and under a solver budget each env's
-        mode and pending action (a parked search itself is not carried: it starts over after an import).  One launch, no sync,
+        mode and pending action (a parked search itself is not carried: it starts over after an import), and with controls
+        each env's control record (active and queued targets, draw counter; not the resampling switch).  One launch, no sync,
         capturable: a captured export writes `out` anew at every replay."""
         if out is None:
             out = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
@@ -414,12 +530,21 @@ def _get(cfg, path, default=None):
 
 def make_smb_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True, sub_batches=1, reward_dtype=torch.float32):
     """make_vec_env's branch for cfg.task.problem == "smb"; everything outside narrow / turtle stepping is refused by name.
+    cfg.controls with cfg.evaluate gives a controllable env; without cfg.evaluate it is refused.
     A positive cfg.task.solver_budget gives smb_ready.SmbReadyVecEnv (asynchronous stepping), absent or 0 an SmbVecEnv."""
     rep = _get(cfg, "representation")
     if rep == "wide":
         _refuse("the wide representation", "the reference's wide fails on a non-square map (wide_rep.py:42, IndexError)")
-    if _get(cfg, "controls") or _get(cfg, "task.controls"):
-        _refuse("controls", "controllable targets are only on the 2-D engine")
+    controls = _get(cfg, "controls") or _get(cfg, "task.controls")
+    if controls and not _get(cfg, "evaluate", False):
+        # rl/envs.py:70-76: without cfg.evaluate the reference's make_env puts a target sampler on top of the ControlWrapper
+        if _get(cfg, "task.alp_gmm", False):
+            _refuse("controls with task.alp_gmm", "the ALP-GMM target sampler is outside the accelerated path: set cfg.evaluate "
+                    "and queue targets, or use set_target_resampling")
+        _refuse("controls without cfg.evaluate", "the reference's make_env then wraps UniformNoiseyTargets, which cannot be "
+                "constructed at its commit (its __init__ reads self.num_params): set cfg.evaluate = True for the plain "
+                "ControlWrapper -- targets through queue_targets -- and call set_target_resampling(True, seed) for that "
+                "wrapper's effect")
     if _get(cfg, "static_prob") is not None or _get(cfg, "n_static_walls") is not None or _get(cfg, "static_tile_wrapper", False):
         _refuse("static tiles", "the static-tile wrapper is only on the 2-D engine")
     if _get(cfg, "act_window") is not None:
@@ -440,6 +565,8 @@ def make_smb_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True
     kw = dict(device=device, obs_window=_get(cfg, "task.obs_window"), weights=_get(cfg, "task.weights"),
               max_board_scans=_get(cfg, "max_board_scans", 3), change_percentage=_get(cfg, "change_percentage"), seeds=seeds,
               auto_reset=auto_reset, solver_power=_get(cfg, "task.solver_power", 10000), reward_dtype=reward_dtype)
+    if controls:  # (ControlWrapper(ctrl_metrics=cfg.controls) alone, cfg.evaluate: rewards in float64, as make_vec_env)
+        kw.update(controls=list(controls), reward_dtype=torch.float64)
     if int(budget) > 0:
         from .smb_ready import SmbReadyVecEnv
         return SmbReadyVecEnv(rep, tuple(_get(cfg, "task.map_shape")), num_envs, solver_budget=int(budget), **kw)
@@ -449,7 +576,9 @@ def make_smb_vec_env(cfg, num_envs, device="cuda:0", seeds=None, auto_reset=True
 class SmbGymEnv:
     """One Mario env with the reference's gym call shape on top of an SmbVecEnv of size 1: reset() -> (obs, {}), step(a) ->
     (obs float32 [oh][ow][8], reward, done, truncated, info).  info holds the nine statistics only on a step that changed the
-    map (pcgrl_env.py:314-332), and always iterations, changes, max_iterations, max_changes."""
+    map (pcgrl_env.py:314-332), and always iterations, changes, max_iterations, max_changes.  With cfg.controls the observation
+    is float32 [oh][ow][2K + 8], the 2K control values broadcast over planes in front (control_wrappers.py:189-214), and
+    set_trgs(trgs) queues targets for the next reset."""
 
     metadata = {"render.modes": []}
 
@@ -460,12 +589,14 @@ class SmbGymEnv:
                                                                  reward_dtype=torch.float64)
         assert self._vec.num_envs == 1 and not self._vec.auto_reset
         v = self._vec
-        self.observation_space = Box(low=0, high=1, shape=v.obs_shape, dtype=np.float32)
+        self.ctrl_metrics = list(getattr(v, "controls", None) or [])
+        shape = tuple(v.obs_shape[:-1]) + (v.obs_shape[-1] + 2 * len(self.ctrl_metrics),)
+        self.observation_space = Box(low=0, high=1, shape=shape, dtype=np.float32)
         self.action_space = Discrete(v.num_actions)
         self.static_trgs = dict(v.spec.static_trgs)
         self.metric_trgs = self.static_trgs
         self.cond_bounds = dict(v.spec.cond_bounds)
-        self.ctrl_metrics = []
+        self._trg_queue = None
         self.metric_weights = dict(v.weights)
         self.metrics = {k: None for k in self.static_trgs}
         self._rep_stats = None
@@ -484,14 +615,29 @@ class SmbGymEnv:
     def _stats_dict(self, row):
         return {k: int(x) for k, x in zip(self._vec.stat_keys, row.tolist())}
 
+    def set_trgs(self, trgs):
+        """ControlWrapper.set_trgs: queued, applied at the next reset (a second call replaces the first)"""
+        self._vec.queue_targets(dict(trgs))
+        self._trg_queue = dict(trgs)
+
+    def _obs_of(self, obs):
+        o = obs[0].float().cpu().numpy()
+        if not self.ctrl_metrics:
+            return o
+        c = self._vec.ctrl_obs[0].cpu().numpy()
+        return np.concatenate((np.broadcast_to(c, o.shape[:-1] + c.shape), o), axis=-1)
+
     def reset(self, *, seed=None, options=None):
         if seed is not None:
             self.seed(seed)
         obs, _ = self._vec.reset()
+        if self._trg_queue is not None:
+            self.metric_trgs.update(self._trg_queue)
+            self._trg_queue = None
         self._rep_stats = self._stats_dict(self._vec.get_state().stats[0].cpu())
         self.metrics = self._rep_stats
         self._changes = 0
-        return obs[0].float().cpu().numpy(), {}
+        return self._obs_of(obs), {}
 
     def step(self, action):
         a = int(action)
@@ -507,7 +653,7 @@ class SmbGymEnv:
         out.update(iterations=int(st.iteration[0]), changes=changes, max_iterations=int(self._vec.max_iterations),
                    max_changes=self._vec.max_changes)
         d = bool(done[0].item())
-        return obs[0].float().cpu().numpy(), float(rew[0].item()), d, d, out
+        return self._obs_of(obs), float(rew[0].item()), d, d, out
 
     def get_map(self):
         return self._vec.get_state().grids[0].cpu().numpy()

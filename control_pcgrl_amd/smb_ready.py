@@ -22,7 +22,9 @@ class SmbReadyVecEnv(SmbVecEnv):
     actions[i] iff it was not busy after the previous launch (after a reset: env_busy()), and every emitted transition belongs to
     the last action the env took.  The observation rows are written for every env in every launch: a busy env's row is the
     observation of the step in flight.  reset() runs the new levels' searches under the budget too and may leave envs busy;
-    get_state() returns the committed state -- for an env with a step in flight, the state before that step."""
+    get_state() returns the committed state -- for an env with a step in flight, the state before that step.  With controls
+    the queued or resampled targets are committed by the launch that draws or injects the new level; an env's ctrl_obs row shows
+    the new level's statistic once its search is over (until then the old level's)."""
 
     def __init__(self, representation, map_shape=(16, 116), num_envs=1, solver_budget=256, **kw):
         budget = int(solver_budget)
@@ -31,7 +33,8 @@ class SmbReadyVecEnv(SmbVecEnv):
         super().__init__(representation, map_shape, num_envs, **kw)
         self._status = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
         self._busy = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
-        self._step_out = (self._obs, self._reward, self._done, self._done, {"stats": self._stats, "status": self._status})
+        self._step_out = (self._obs, self._reward, self._done, self._done,
+                          dict(self._step_out[4], stats=self._stats, status=self._status))
         self.park_bytes = int(self._L.pcgrl_smb_ready_park_bytes(C.byref(self.cfg)))
         self.set_solver_budget(budget)
 
