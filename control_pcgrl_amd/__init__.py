@@ -12,6 +12,8 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
                            -- or per K steps: rollout(), with given actions or actions drawn on the device
   SmbReadyVecEnv           the same with cfg.task.solver_budget: a bounded, resumable play-through per launch and a status byte
                            (both take cfg.controls / controls=[...]: per-env targets, queue_targets, ctrl_obs, resampling)
+  SmbVectorEnv             the same envs behind the VectorEnv call shape, the float32 Box image written once by a kernel of
+                           its own; make_vector_env(cfg, n) picks SmbVectorEnv or PcgrlVectorEnv by problem
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of
@@ -26,5 +28,6 @@ from .dist import EpisodeStatsReducer, shard_env_range  # noqa: F401
 from .smb import SmbEvaluator, smb_spec  # noqa: F401
 from .smb_env import SmbGymEnv, SmbVecEnv  # noqa: F401
 from .smb_ready import SmbReadyVecEnv  # noqa: F401
+from .smb_rllib import SmbVectorEnv, make_vector_env  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

@@ -47,6 +47,8 @@
 #include "smb/pcgrl_smb_rollout.h"  // K steps in one launch, device-drawn actions
 #include "../../include/pcgrl_amd_smb_ctrl.h"
 #include "smb/pcgrl_smb_ctrl.h"  // controllable generation: per-env targets
+#include "../../include/pcgrl_amd_smb_vector.h"
+#include "smb/pcgrl_smb_vector.h"  // the float32 hand-out (RLlib's Box form)
 
 using namespace pcgrl;
 
@@ -2874,6 +2876,44 @@ int pcgrl_smb_ctrl_get(pcgrl_smb_env_handle h, double *d_active, double *d_shown
   ga.queued = d_queued;
   ga.flags = d_flags;
   HIPCHK(launch_smb_ctrl_get(ga, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------- Super Mario Bros environments: the float32 hand-out
+// include/pcgrl_amd_smb_vector.h; the kernel in smb/pcgrl_smb_vector.h.
+
+extern "C" {
+
+int64_t pcgrl_smb_env_obs_f32_bytes(pcgrl_smb_env_handle h) {
+  if (!h) return -1;
+  return (int64_t)h->a.oh * h->a.ow * (2 * h->ctrl.n_ctrl + SMB_TILES + 1) * (int64_t)sizeof(float);
+}
+
+int pcgrl_smb_env_observe_f32(pcgrl_smb_env_handle h, float *out, void *stream) {
+  const char *who = "pcgrl_smb_env_observe_f32";
+  if (!h || !out) return fail(PCGRL_EINVAL, std::string(who) + ": null handle or output");
+  if ((uintptr_t)out & 7u) return fail(PCGRL_EINVAL, std::string(who) + ": the output must be 8-byte aligned");
+  if (h->budget > 0)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": a solver budget is set: a busy env's committed state is not the state "
+                                                       "of the step in flight (pcgrl_smb_ready_set_budget(h, 0) first)");
+  if (h->ctrl.n_ctrl > 0 && !h->a.ctrl.obs)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the controls were attached without a control observation buffer");
+  ON_DEVICE(h->device);
+  SmbVectorArgs va = {};
+  va.h = h->a.h;
+  va.w = h->a.w;
+  va.oh = h->a.oh;
+  va.ow = h->a.ow;
+  va.n = h->a.n;
+  va.map_stride = h->a.map_stride;
+  va.n_ctrl = h->ctrl.n_ctrl;
+  va.maps = h->a.maps;
+  va.st = h->a.st;
+  va.ctrl_obs = h->a.ctrl.obs;
+  va.out = out;
+  HIPCHK(launch_smb_vector_obs(va, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

@@ -118,7 +118,101 @@ def _hip_runtime():
     return _lib.lib()
 
 
-class PcgrlVectorEnv(_Base):
+class _VectorAdapter:
+    """What the VectorEnv adapters of this package share (PcgrlVectorEnv here, smb_rllib.SmbVectorEnv): the leases of pinned
+    blocks, the bookkeeping of finished and freshly reset envs, the sub-env accessors and RLlib's reset calls.  A subclass has
+    `vec` (the batched env), `_total` (bytes of a call's block), `_views(lease)` (numpy views obs / rew / stats / done over a
+    block) and `_masked_reset(mask)` (one launch for the envs of `mask`, ending in `_took_reset`)."""
+
+    def _adapter_state(self):
+        N = self.num_envs
+        self._free = []  # pinned host blocks no array refers to any more
+        self._stats = np.zeros((N, len(self.vec.stat_keys)), np.int32)  # the envs' current statistics (sub-env accessors)
+        self._pending = np.zeros(N, np.bool_)   # finished, waiting for RLlib's reset_at
+        self._fresh = np.zeros(N, np.bool_)     # already reset by the batched launch, reset_at only hands the obs out
+        self._reset_obs = None                  # observations of the last batched reset (a block of their own)
+        self._iter = np.zeros(N, np.int64)
+        self._subs = [_SubEnv(self, i) for i in range(N)]
+        self._queued_trgs = {}  # env index -> targets set since its last reset
+
+    def _lease(self):
+        return _Lease(self._free.pop() if self._free else torch.empty(self._total, dtype=torch.uint8).pin_memory(), self._free)
+
+    def _took_reset(self, mask, r):
+        """after a masked reset whose block is `r`: its observations, and for the masked envs the statistics and targets"""
+        self._reset_obs = r["obs"]
+        self._stats[mask] = r["stats"][mask]
+        self._iter[mask] = 0
+        for i in [i for i in self._queued_trgs if mask[i]]:  # the queued targets are the envs' targets from here on
+            self._subs[i].metric_trgs.update(self._queued_trgs.pop(i))
+
+    def _took_step(self, r):
+        """after a step whose block is `r`: the bookkeeping, and vector_step's return value"""
+        self._stats[...] = r["stats"]
+        self._iter += 1
+        self._pending |= r["done"]
+        self._fresh[:] = False
+        done = r["done"].tolist()
+        return list(r["obs"]), r["rew"].tolist(), done, list(done), _Infos(self, r["stats"], self._iter.copy())
+
+    def stats_dict(self, i):
+        return {k: int(x) for k, x in zip(self.vec.stat_keys, self._stats[i])}
+
+    def _info(self, stats_row, it):
+        d = {k: int(x) for k, x in zip(self.vec.stat_keys, stats_row)}
+        d.update(iterations=int(it), max_iterations=int(self.vec.cfg.max_iterations),
+                 max_changes=None if self.vec.cfg.max_changes < 0 else int(self.vec.cfg.max_changes))
+        return d
+
+    def info_dict(self, i):
+        return self._info(self._stats[i], self._iter[i])
+
+    def set_trgs(self, trgs, index=None):
+        """ControlWrapper.set_trgs for one env (index) or the whole batch: queued, applied at the next reset"""
+        mask = None
+        if index is not None:
+            mask = np.zeros(self.num_envs, np.uint8)
+            mask[int(index)] = 1
+        self.vec.queue_targets({k: (x if isinstance(x, tuple) else float(x)) for k, x in trgs.items()}, mask=mask)
+        for i in (range(self.num_envs) if index is None else (int(index),)):
+            self._queued_trgs.setdefault(i, {}).update(trgs)
+
+    # -- VectorEnv API (the step is the subclass's) -----------------------------------------------
+    def vector_reset(self, *, seeds=None, options=None):
+        if seeds is not None and any(s is not None for s in seeds):
+            self.vec.seed([0 if s is None else int(s) for s in seeds])
+        self._masked_reset(np.ones(self.num_envs, np.bool_))
+        self._pending[:] = False
+        self._fresh[:] = False
+        return list(self._reset_obs), [{} for _ in range(self.num_envs)]
+
+    def reset_at(self, index=None, *, seed=None, options=None):
+        i = 0 if index is None else int(index)
+        if seed is not None:
+            raise NotImplementedError("per-env reseeding goes through vector_reset(seeds=...) / VecPcgrlEnv.seed")
+        if not self._fresh[i]:
+            mask = self._pending.copy()
+            mask[i] = True
+            self._masked_reset(mask)  # every env that finished in the last step, in one launch
+            self._fresh |= mask
+            self._pending[:] = False
+        self._fresh[i] = False
+        return self._reset_obs[i], {}
+
+    def restart_at(self, index=None):
+        return self.reset_at(index)[0]
+
+    def get_sub_environments(self):
+        return self._subs
+
+    def try_render_at(self, index=None):
+        return None
+
+    def close(self):
+        self.vec.close()
+
+
+class PcgrlVectorEnv(_VectorAdapter, _Base):
     DIRECT_MAX_BYTES = 1 << 20  # default: the step kernel writes into host memory itself when a call's outputs are <= 1 MiB
     HOST_CONVERT_MAX_BYTES = 1 << 18  # float32 hand-out: uint8 -> float32 on the host up to this many observation bytes per call
 
@@ -128,8 +222,8 @@ class PcgrlVectorEnv(_Base):
             raise NotImplementedError("PcgrlVectorEnv with multiagent.n_agents: RLlib's VectorEnv has one agent per sub-env; use "
                                       "multiagent.MultiAgentVecEnv (batched) or make_env(cfg) (the reference's dict call shape)")
         if (vec is None and _cfg_get(cfg, "task.problem") == "smb") or type(vec).__name__ == "SmbVecEnv":
-            raise NotImplementedError("PcgrlVectorEnv with smb: the RLlib adapter drives VecPcgrlEnv's engine handle (host-mapped "
-                                      "outputs, masked resets per sub-env); step smb through SmbVecEnv or make_env(cfg)")
+            raise NotImplementedError("PcgrlVectorEnv with smb: this adapter drives VecPcgrlEnv's engine handle; smb has an adapter "
+                                      "of its own, smb_rllib.SmbVectorEnv (make_vector_env(cfg, n) picks the class by problem)")
         self.vec = vec if vec is not None else make_vec_env(cfg, num_envs, device=device, seeds=seeds, auto_reset=False)
         v = self.vec
         assert not v.auto_reset, "PcgrlVectorEnv drives resets itself (RLlib calls reset_at)"
@@ -157,7 +251,6 @@ class PcgrlVectorEnv(_Base):
         self._o_done = self._o_stats + up(N * S * 4)
         self._o_ctrl = self._o_done + up(N)
         self._total = self._o_ctrl + up(N * max(self.n_ctrl_planes, 1) * 4)
-        self._free = []  # pinned host blocks no array refers to any more
         self._dev = torch.zeros(self._total, dtype=torch.uint8, device=v.device)
         base = self._dev.data_ptr()
         self._dp = dict(obs=base, rew=base + self._o_rew, stats=base + self._o_stats, done=base + self._o_done, ctrl=base + self._o_ctrl)
@@ -189,18 +282,9 @@ class PcgrlVectorEnv(_Base):
         self._act_np = self._act.numpy()
         # small batches: the kernel reads the actions from pinned host memory itself (no host->device copy to issue)
         self._act_dev = self._act if self._direct else torch.zeros((N, v.action_entries), dtype=torch.int32, device=v.device)
-        self._stats = np.zeros((N, S), np.int32)  # the envs' current statistics (sub-env accessors)
-        self._pending = np.zeros(N, np.bool_)   # finished, waiting for RLlib's reset_at
-        self._fresh = np.zeros(N, np.bool_)     # already reset by the batched launch, reset_at only hands the obs out
-        self._reset_obs = None                  # observations of the last batched reset (a block of their own)
-        self._iter = np.zeros(N, np.int64)
-        self._subs = [_SubEnv(self, i) for i in range(N)]
-        self._queued_trgs = {}  # env index -> targets set since its last reset
+        self._adapter_state()
 
     # -- helpers -----------------------------------------------------------------------------------
-    def _lease(self):
-        return _Lease(self._free.pop() if self._free else torch.empty(self._total, dtype=torch.uint8).pin_memory(), self._free)
-
     def _views(self, lease):
         """numpy views of a call's block (they keep the lease, and so the block, alive)"""
         h = np.asarray(lease)
@@ -246,28 +330,6 @@ class PcgrlVectorEnv(_Base):
         b = lease.ptr
         return b, b + self._o_rew, b + self._o_stats, b + self._o_done, b + self._o_ctrl
 
-    def stats_dict(self, i):
-        return {k: int(x) for k, x in zip(self.vec.stat_keys, self._stats[i])}
-
-    def _info(self, stats_row, it):
-        d = {k: int(x) for k, x in zip(self.vec.stat_keys, stats_row)}
-        d.update(iterations=int(it), max_iterations=int(self.vec.cfg.max_iterations),
-                 max_changes=None if self.vec.cfg.max_changes < 0 else int(self.vec.cfg.max_changes))
-        return d
-
-    def info_dict(self, i):
-        return self._info(self._stats[i], self._iter[i])
-
-    def set_trgs(self, trgs, index=None):
-        """ControlWrapper.set_trgs for one env (index) or the whole batch: queued, applied at the next reset"""
-        mask = None
-        if index is not None:
-            mask = np.zeros(self.num_envs, np.uint8)
-            mask[int(index)] = 1
-        self.vec.queue_targets({k: (x if isinstance(x, tuple) else float(x)) for k, x in trgs.items()}, mask=mask)
-        for i in (range(self.num_envs) if index is None else (int(index),)):
-            self._queued_trgs.setdefault(i, {}).update(trgs)
-
     def _masked_reset(self, mask):
         """one launch for every env in `mask`; the observations go to a block of their own and, for the masked envs only,
         the statistics into the current ones"""
@@ -282,37 +344,7 @@ class PcgrlVectorEnv(_Base):
         if self.n_ctrl_planes:
             _lib.check(L.pcgrl_ctrl_observe(v._h, ctrl_p, s), "pcgrl_ctrl_observe")
         self._finish(lease, s)
-        r = self._views(lease)
-        self._reset_obs = r["obs"]
-        self._stats[mask] = r["stats"][mask]
-        self._iter[mask] = 0
-        for i in [i for i in self._queued_trgs if mask[i]]:  # the queued targets are the envs' targets from here on
-            self._subs[i].metric_trgs.update(self._queued_trgs.pop(i))
-
-    # -- VectorEnv API -----------------------------------------------------------------------------
-    def vector_reset(self, *, seeds=None, options=None):
-        if seeds is not None and any(s is not None for s in seeds):
-            self.vec.seed([0 if s is None else int(s) for s in seeds])
-        self._masked_reset(np.ones(self.num_envs, np.bool_))
-        self._pending[:] = False
-        self._fresh[:] = False
-        return list(self._reset_obs), [{} for _ in range(self.num_envs)]
-
-    def reset_at(self, index=None, *, seed=None, options=None):
-        i = 0 if index is None else int(index)
-        if seed is not None:
-            raise NotImplementedError("per-env reseeding goes through vector_reset(seeds=...) / VecPcgrlEnv.seed")
-        if not self._fresh[i]:
-            mask = self._pending.copy()
-            mask[i] = True
-            self._masked_reset(mask)  # every env that finished in the last step, in one launch
-            self._fresh |= mask
-            self._pending[:] = False
-        self._fresh[i] = False
-        return self._reset_obs[i], {}
-
-    def restart_at(self, index=None):
-        return self.reset_at(index)[0]
+        self._took_reset(mask, self._views(lease))
 
     def vector_step(self, actions):
         v = self.vec
@@ -330,19 +362,4 @@ class PcgrlVectorEnv(_Base):
         if rc:
             _lib.check(rc, "pcgrl_step")
         self._finish(lease, s)  # the one device -> host copy of the call
-        r = self._views(lease)
-        self._stats[...] = r["stats"]
-        self._iter += 1
-        self._pending |= r["done"]
-        self._fresh[:] = False
-        done = r["done"].tolist()
-        return list(r["obs"]), r["rew"].tolist(), done, list(done), _Infos(self, r["stats"], self._iter.copy())
-
-    def get_sub_environments(self):
-        return self._subs
-
-    def try_render_at(self, index=None):
-        return None
-
-    def close(self):
-        self.vec.close()
+        return self._took_step(self._views(lease))

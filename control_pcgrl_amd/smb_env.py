@@ -366,6 +366,36 @@ class SmbVecEnv:
         _lib.check(self._L.pcgrl_smb_env_observe(self._handle(), self._obs.data_ptr(), self._stream()), "pcgrl_smb_env_observe")
         return self._obs
 
+    # -- the pointer-level surface an adapter drives (smb_rllib.SmbVectorEnv): caller-given device or host-mapped pinned buffers,
+    #    one launch per call on `stream`, the status code returned (VecPcgrlEnv has the same names for the engine's problems) -----
+    def step_into(self, actions_ptr, obs_ptr, reward_ptr, reward64_ptr, done_ptr, stats_ptr, stream):
+        """pcgrl_smb_env_step: any output may be None; obs_ptr is the uint8 observation (16-byte aligned)"""
+        return self._L.pcgrl_smb_env_step(self._handle(), actions_ptr, 1 if self.auto_reset else 0, obs_ptr, reward_ptr,
+                                          reward64_ptr, done_ptr, stats_ptr, stream)
+
+    def observe_into(self, obs_ptr, stream):
+        """the uint8 observation of the committed state"""
+        return self._L.pcgrl_smb_env_observe(self._handle(), obs_ptr, stream)
+
+    @property
+    def obs_f32_shape(self):
+        """one env's float32 image: [oh][ow][2K + 8], the control planes in front"""
+        return self.obs_window + (2 * len(self.controls) + len(SMB_TILES) + 1,)
+
+    def observe_f32_into(self, ptr, stream):
+        """The float32 image of the committed state, float32 [N] + obs_f32_shape, written once by a kernel of its own
+        (include/pcgrl_amd_smb_vector.h); after a reset / step on the same stream.  ptr: 8-byte aligned."""
+        return self._L.pcgrl_smb_env_observe_f32(self._handle(), ptr, stream)
+
+    def reset_masked(self, mask_ptr, stream, obs_ptr=None):
+        """pcgrl_smb_env_reset of the envs of the uint8 mask (None = all), drawn maps; obs_ptr None writes no observation"""
+        with torch.cuda.device(self.device):
+            return self._L.pcgrl_smb_env_reset(self._handle(), mask_ptr, None, None, obs_ptr, stream)
+
+    def stats_into(self, ptr, stream):
+        """the committed statistics, int32 [N][9]"""
+        return self._L.pcgrl_smb_env_get_state(self._handle(), None, None, None, ptr, None, None, None, stream)
+
     def get_state(self):
         """grids uint8 [N][H][W], pos int32 [N][2], iteration, changes, n_step (narrow's scan counter), searches (play-throughs
         run since the env was made), stats int32 [N][9], last_loss, ep_return float64 [N], search_iterations int64 [N] and
