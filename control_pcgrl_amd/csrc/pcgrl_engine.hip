@@ -49,6 +49,8 @@
 #include "smb/pcgrl_smb_ctrl.h"  // controllable generation: per-env targets
 #include "../../include/pcgrl_amd_smb_vector.h"
 #include "smb/pcgrl_smb_vector.h"  // the float32 hand-out (RLlib's Box form)
+#include "../../include/pcgrl_amd_smb_measures.h"
+#include "smb/pcgrl_smb_measures.h"  // level measures and pairwise Hamming diversity of smb maps
 
 using namespace pcgrl;
 
@@ -2915,6 +2917,137 @@ int pcgrl_smb_env_observe_f32(pcgrl_smb_env_handle h, float *out, void *stream) 
   va.out = out;
   HIPCHK(launch_smb_vector_obs(va, (hipStream_t)stream));
   return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- Super Mario Bros maps: level measures and pairwise Hamming diversity
+// include/pcgrl_amd_smb_measures.h; the measure / pack kernel in smb/pcgrl_smb_measures.h, the pairwise kernels those of
+// measures/pcgrl_measures.h.
+
+static int smb_meas_check_shape(const char *who, int32_t h, int32_t w) {
+  if (h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 4..16 rows and 1..128 columns only (the shapes the smb "
+                                                       "evaluator takes)");
+  return PCGRL_OK;
+}
+
+static void smb_meas_args(SmbMeasArgs &a, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, const pcgrl_smb_env *env) {
+  a = SmbMeasArgs{};
+  a.grids = d_grids;
+  if (env) {
+    a.maps = env->a.maps;
+    a.map_stride = env->a.map_stride;
+  }
+  a.h = h;
+  a.w = w;
+  a.n = n;
+  a.NW = (h * w + 63) / 64;
+  a.group = 1;
+}
+
+// the checks of a measures call, before any HIP call (`env`: the handle's maps, no d_grids)
+static int smb_measures_check(const char *who, bool env, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids,
+                              const int32_t *d_counts, const int32_t *d_match, const double *d_entropy, const double *d_tab) {
+  if (n < 0 || (n > 0 && (!d_counts || !d_match || (d_entropy && !d_tab) || (!env && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  return smb_meas_check_shape(who, h, w);
+}
+
+static int smb_measures_enqueue(SmbMeasArgs &a, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
+                                const double *d_tab, void *stream) {
+  a.counts = d_counts;
+  a.match = d_match;
+  a.forms = d_forms;
+  a.entropy = d_entropy;
+  a.tab = d_tab;
+  HIPCHK(launch_smb_measures(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+static int smb_diversity_check(const char *who, bool env, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
+                               const void *d_scratch, const int64_t *d_sum) {
+  if (n < 0 || (n > 0 && (!d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum || (!env && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (group < 2 || n % group != 0)
+    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
+  return smb_meas_check_shape(who, h, w);
+}
+
+// pack the n maps into d_scratch, then the all-pairs kernel per group and the finish
+static int smb_diversity_enqueue(SmbMeasArgs &a, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores,
+                                 int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  a.pack = (uint64_t *)d_scratch;
+  a.sum = (unsigned long long *)d_sum;
+  a.near_key = (unsigned long long *)(a.pack + (size_t)a.n * SMB_MEAS_PLANES * a.NW);
+  a.group = group;
+  HIPCHK(launch_smb_measures(a, (hipStream_t)stream));
+  DivArgs d;
+  d.pack = a.pack;
+  d.n = a.n;
+  d.K = group;
+  d.P = SMB_MEAS_PLANES;
+  d.NW = a.NW;
+  div_splits(a.n, group, d.splits, d.tiles_per_split);
+  d.sum = a.sum;
+  d.near_key = a.near_key;
+  d.pairwise = d_pairwise;
+  HIPCHK(launch_diversity(d, (hipStream_t)stream));
+  if (d_scores || d_nearest || d_nearest_idx)
+    HIPCHK(launch_diversity_finish(d, a.h * a.w, d_nearest, d_nearest_idx, d_scores, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+extern "C" {
+
+int pcgrl_smb_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
+                                 double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
+  const int rc = smb_measures_check("pcgrl_smb_measures_for_grids", false, h, w, n, d_grids, d_counts, d_match, d_entropy,
+                                    d_entropy_tab);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  SmbMeasArgs a;
+  smb_meas_args(a, h, w, n, d_grids, nullptr);
+  return smb_measures_enqueue(a, d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
+}
+
+size_t pcgrl_smb_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
+  if (n <= 0 || h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W) return 0;
+  // the bit-plane image, then one nearest-map key per map
+  return (size_t)n * (SMB_MEAS_PLANES * ((h * w + 63) / 64) + 1) * sizeof(uint64_t);
+}
+
+int pcgrl_smb_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch,
+                                  int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
+                                  int32_t *d_pairwise, void *stream) {
+  const int rc = smb_diversity_check("pcgrl_smb_diversity_for_grids", false, h, w, n, d_grids, group, d_scratch, d_sum);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  SmbMeasArgs a;
+  smb_meas_args(a, h, w, n, d_grids, nullptr);
+  return smb_diversity_enqueue(a, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+}
+
+int pcgrl_smb_env_measures(pcgrl_smb_env_handle h, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
+                           const double *d_entropy_tab, void *stream) {
+  const char *who = "pcgrl_smb_env_measures";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  const int rc = smb_measures_check(who, true, h->a.h, h->a.w, h->a.n, nullptr, d_counts, d_match, d_entropy, d_entropy_tab);
+  if (rc != PCGRL_OK) return rc;
+  ON_DEVICE(h->device);
+  SmbMeasArgs a;
+  smb_meas_args(a, h->a.h, h->a.w, h->a.n, nullptr, h);
+  return smb_measures_enqueue(a, d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
+}
+
+int pcgrl_smb_env_diversity(pcgrl_smb_env_handle h, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores,
+                            int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  const char *who = "pcgrl_smb_env_diversity";
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
+  const int rc = smb_diversity_check(who, true, h->a.h, h->a.w, h->a.n, nullptr, group, d_scratch, d_sum);
+  if (rc != PCGRL_OK) return rc;
+  ON_DEVICE(h->device);
+  SmbMeasArgs a;
+  smb_meas_args(a, h->a.h, h->a.w, h->a.n, nullptr, h);
+  return smb_diversity_enqueue(a, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"

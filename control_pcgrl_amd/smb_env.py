@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .problems import target_interval
-from .smb import MAX_H, MAX_SOLVER_POWER, MAX_W, MIN_H, SMB_TILES, smb_config, smb_spec
+from .smb import MAX_H, MAX_SOLVER_POWER, MAX_W, MIN_H, SMB_TILES, SmbMeasures, smb_config, smb_spec
 
 REPS = {"narrow": 0, "turtle": 1}
 MAX_OBS_WINDOW = 255  # Cropped.set_pad_size keeps the pad as int8: the reference fails above
@@ -47,7 +47,7 @@ def _refuse(what, why):
     raise NotImplementedError(f"smb: {what} is not stepped on the device: {why}")
 
 
-class SmbVecEnv:
+class SmbVecEnv(SmbMeasures):
     """N Mario envs on one device with VecPcgrlEnv's conventions: torch tensors in and out, one HIP launch per step(), output
     tensors owned by the env and overwritten by the next call.  There is no CPU fallback.
 
@@ -415,6 +415,28 @@ class SmbVecEnv:
                                searches=counters[:, 3], stats=stats, last_loss=last_loss, ep_return=ep_return,
                                search_iterations=iters[:, 0], max_search_iterations=iters[:, 1])
 
+    # -- level measures and pairwise Hamming diversity (include/pcgrl_amd_smb_measures.h) ----------------
+    def measures(self, entropy=True):
+        """The behaviour characteristics of every env's committed map (evo/evolve.py:606-635 get_bc), field for field
+        VecPcgrlEnv.measures with T = 7; read from the handle's maps, no copy.  Under a solver budget a busy env's step in
+        flight is not shown, as in get_state().  One launch on the current stream, no host sync."""
+        return self._measures(self._handle(), self.num_envs, None, entropy)
+
+    def measures_for_grids(self, grids, entropy=True):
+        """measures() of caller maps (any number of them, uint8 tile ids of this env's map shape)."""
+        g = self._grids_arg(grids)
+        return self._measures(None, g.shape[0], g, entropy)
+
+    def diversity(self, group=None, pairwise=False):
+        """Pairwise Hamming distances among the envs' committed maps in consecutive groups of `group` maps (None: one group of
+        all), field for field VecPcgrlEnv.diversity.  Three launches on the current stream, no host sync."""
+        return self._diversity(self._handle(), self.num_envs, None, group, pairwise)
+
+    def diversity_for_grids(self, grids, group=None, pairwise=False):
+        """diversity() of caller maps (any number of them, uint8 tile ids of this env's map shape)."""
+        g = self._grids_arg(grids)
+        return self._diversity(None, g.shape[0], g, group, pairwise)
+
     def last_episode(self):
         """The last finished episode of every env: ep_return float64 [N], length int32 [N], stats int32 [N][9], count int32 [N]
         (how many episodes the env has finished; the other rows mean nothing while it is 0)."""
@@ -687,6 +709,15 @@ class SmbGymEnv:
 
     def get_map(self):
         return self._vec.get_state().grids[0].cpu().numpy()
+
+    @property
+    def measures(self):
+        """The behaviour characteristics of the current map under get_bc's names (evo/evolve.py:606-635) as Python floats, and
+        "tile_fractions", get_counts' list (evolve.py:449-464): the dict PcgrlGymEnv.measures returns."""
+        m = self._vec.measures()
+        out = {k: float(v[0].item()) for k, v in m.bc.items()}
+        out["tile_fractions"] = [float(x) for x in m.tile_fractions[0].cpu().tolist()]
+        return out
 
     def close(self):
         self._vec.close()
