@@ -15,7 +15,9 @@
 //             LDS per wave, one wave per CU); the latency is hidden by occupancy instead -- 4.5 KB of LDS and one wave per
 //             level let a CU hold 32 levels.  The open list is CPython's heapq (heappush = append + _siftdown, heappop =
 //             move the last item to the root, _siftup to a leaf along the smaller children, _siftdown back), ordered by f
-//             alone with `<`, because the sift order decides which of several equal-f nodes is expanded first.
+//             alone with `<`, because the sift order decides which of several equal-f nodes is expanded first.  The loop body is
+//             smb_search_iteration, the start smb_search_start and the finished search's tail smb_play_result: the budgeted,
+//             resumable search of smb/pcgrl_smb_ready.h runs the same three.
 //   memory    per level a workspace slot in HBM: nodes (8 B: x 8 | y+5 5 | airTime 3 | jumps 14 | action 2 ; parent 17 |
 //             depth 14) and heap entries (4 B: f 15 | node 17), 4 * power + 1 of each -- an expansion pushes four, and there
 //             are at most `power` expansions.  Both arrays are written before they are read (count-bounded), so a dirty
@@ -30,6 +32,7 @@
 
 namespace pcgrl {
 
+constexpr int SMB_TILES = 7;
 constexpr int SMB_STATS = 9;  // dist-floor, disjoint-tubes, enemies, empty, noise, jumps, jumps-dist, dist-win, sol-length
 constexpr int SMB_MAX_H = 16, SMB_MIN_H = 4, SMB_MAX_W = 128;
 constexpr int SMB_MAX_POWER = 16000;  // depth, jumps < 2^14; f < 2^15; 4 * power + 1 nodes < 2^17
@@ -80,6 +83,35 @@ struct SmbPlayOut {
   int16_t *jump_locs;
   int32_t cap, jump_cap;
 };
+
+// a map byte as the kernels read it: a tile id above 6 reads as empty and sets `bad` (the caller raises its error bit)
+__device__ __forceinline__ uint8_t smb_tile(uint8_t t, bool &bad) {
+  if (t >= SMB_TILES) {
+    bad = true;
+    return 0;
+  }
+  return t;
+}
+
+// One term of ControlWrapper.get_loss: -(distance of the statistic to its zero-loss interval [lo, hi]) * weight, rounded to
+// double before it is added (no fused multiply-add): the Python rules bit for bit whatever the targets.
+__device__ __forceinline__ double smb_target_term(int32_t stat, double lo, double hi, double weight) {
+#pragma clang fp contract(off)
+  const double v = (double)stat;
+  const double d = v < lo ? lo - v : (v > hi ? v - hi : 0.0);
+  return -d * weight;
+}
+
+// ControlWrapper.get_loss: the terms of the statistics that have a target, added in the statistics' order.  Unrolled, for the
+// callers that hold the statistics in registers.
+__device__ __forceinline__ double smb_target_loss(const int32_t *has_trg, const double *weight, const double *lo, const double *hi,
+                                                  const int32_t *stats) {
+  double loss = 0.0;
+#pragma unroll
+  for (int k = 0; k < SMB_STATS; k++)
+    if (has_trg[k]) loss = loss + smb_target_term(stats[k], lo[k], hi[k], weight[k]);
+  return loss;
+}
 
 __device__ __forceinline__ int smb_wave_sum(int v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -150,62 +182,83 @@ __device__ __forceinline__ int smb_naction(uint2 v) { return v.x >> 30; }
 __device__ __forceinline__ uint32_t smb_nparent(uint2 v) { return v.y & 0x1FFFFu; }
 __device__ __forceinline__ int smb_ndepth(uint2 v) { return v.y >> 17; }
 
+// A search before its first iteration: the start node alone in the open list, nothing expanded and no best node yet.  The
+// caller's lanes take the loop's words; nodes[0] and heap[0] are written by the lane(s) that call it with `write`.  This is also
+// what "parked after 0 iterations" means (smb/pcgrl_smb_ready.h, smb/pcgrl_smb_state.h), with a zeroed visited set.
+__device__ __forceinline__ void smb_search_start(uint2 *nodes, uint32_t *heap, int H, int W, bool write, int &it, int &nn, int &hn,
+                                                 uint32_t &best, int &best_x, int &best_depth) {
+  if (write) {
+    nodes[0] = smb_pack(1, H - 3, 0, 0, 0, SMB_NO_PARENT, 0);
+    heap[0] = (uint32_t)(W + 4 - 1) << 17;
+  }
+  it = 0, nn = 1, hn = 1, best = 0, best_x = -1, best_depth = 0;
+}
+
+// One iteration of AStarAgent.getSolution's loop (one lane): pops the open list's first node and expands it; true when that node
+// wins (`best` is then the winner).  The only A* loop body of the library: smb_search runs it to the end, smb_play_budgeted of
+// smb/pcgrl_smb_ready.h under a launch's budget.
+__device__ __forceinline__ bool smb_search_iteration(const uint16_t *col, uint32_t *seen, uint2 *nodes, uint32_t *heap, int H,
+                                                     int LW, int ex, int balance, int &nn, int &hn, uint32_t &best, int &best_x,
+                                                     int &best_depth) {
+  const uint32_t cur = smb_heap_pop(heap, hn) & 0x1FFFFu;
+  const uint2 nd = nodes[cur];
+  const int x = smb_nx(nd), y = smb_ny(nd), air = smb_nair(nd), jumps = smb_njumps(nd), depth = smb_ndepth(nd);
+  if (y >= H) return false;  // a lose node
+  if (x >= ex) {
+    best = cur;
+    return true;
+  }
+  const int bit = (x * 21 + (y + 5)) * 6 + air;
+  if ((seen[bit >> 5] >> (bit & 31)) & 1u) return false;
+  if (x > best_x || (x == best_x && depth < best_depth)) {  // a smaller ex - x, or the same with a smaller depth
+    best = cur;
+    best_x = x;
+    best_depth = depth;
+  }
+  seen[bit >> 5] |= 1u << (bit & 31);
+  // State.update for the four actions (dx, dy) = (0,0), (1,0), (0,-1), (1,-1)
+  const bool ground = (y >= -1 && y < H - 1) ? ((col[x] >> (y + 1)) & 1u) != 0 : false;
+  const bool right = smb_movable(col, H, LW, x + 1, y);
+  for (int a = 0; a < 4; a++) {
+    const int cx = ((a & 1) && right) ? x + 1 : x;
+    int cy = y, cair = air, cj = jumps;
+    if (a & 2) {
+      if (ground && smb_movable(col, H, LW, cx, y - 1)) {
+        cair = 5;
+        cj++;
+      }
+    } else if (cair > 0) {
+      cair = 1;
+    }
+    if (cair > 1) {
+      cair--;
+      if (smb_movable(col, H, LW, cx, y - 1)) cy = y - 1;
+      else cair = 1;
+    } else if (cair == 1) {
+      cair = 0;
+    } else if (smb_movable(col, H, LW, cx, y + 1)) {
+      cy = y + 1;
+    }
+    nodes[nn] = smb_pack(cx, cy, cair, cj, a, cur, depth + 1);
+    smb_heap_push(heap, hn, ((uint32_t)((ex - cx) + balance * (depth + 1)) << 17) | (uint32_t)nn);
+    nn++;
+  }
+  return false;
+}
+
 // AStarAgent.getSolution on the level in col[] (one lane): returns the node it ends on -- the winner, else the best node --
 // and the iterations it ran.  `seen` must be zero on entry.
 __device__ inline uint32_t smb_search(const uint16_t *col, uint32_t *seen, uint2 *nodes, uint32_t *heap, int H, int W, int power,
                                       int balance, int &iterations, bool &won) {
-  const int LW = W + 6, ex = W + 4;
-  int nn = 1, hn = 1, it = 0;
-  nodes[0] = smb_pack(1, H - 3, 0, 0, 0, SMB_NO_PARENT, 0);
-  heap[0] = (uint32_t)(ex - 1) << 17;
-  uint32_t best = 0;
-  int best_x = -1, best_depth = 0;
+  int it, nn, hn, best_x, best_depth;
+  uint32_t best;
+  smb_search_start(nodes, heap, H, W, true, it, nn, hn, best, best_x, best_depth);
   won = false;
   while (it < power && hn > 0) {
     it++;
-    const uint32_t cur = smb_heap_pop(heap, hn) & 0x1FFFFu;
-    const uint2 nd = nodes[cur];
-    const int x = smb_nx(nd), y = smb_ny(nd), air = smb_nair(nd), jumps = smb_njumps(nd), depth = smb_ndepth(nd);
-    if (y >= H) continue;  // a lose node
-    if (x >= ex) {
+    if (smb_search_iteration(col, seen, nodes, heap, H, W + 6, W + 4, balance, nn, hn, best, best_x, best_depth)) {
       won = true;
-      best = cur;
       break;
-    }
-    const int bit = (x * 21 + (y + 5)) * 6 + air;
-    if ((seen[bit >> 5] >> (bit & 31)) & 1u) continue;
-    if (x > best_x || (x == best_x && depth < best_depth)) {  // a smaller ex - x, or the same with a smaller depth
-      best = cur;
-      best_x = x;
-      best_depth = depth;
-    }
-    seen[bit >> 5] |= 1u << (bit & 31);
-    // State.update for the four actions (dx, dy) = (0,0), (1,0), (0,-1), (1,-1)
-    const bool ground = (y >= -1 && y < H - 1) ? ((col[x] >> (y + 1)) & 1u) != 0 : false;
-    const bool right = smb_movable(col, H, LW, x + 1, y);
-    for (int a = 0; a < 4; a++) {
-      const int cx = ((a & 1) && right) ? x + 1 : x;
-      int cy = y, cair = air, cj = jumps;
-      if (a & 2) {
-        if (ground && smb_movable(col, H, LW, cx, y - 1)) {
-          cair = 5;
-          cj++;
-        }
-      } else if (cair > 0) {
-        cair = 1;
-      }
-      if (cair > 1) {
-        cair--;
-        if (smb_movable(col, H, LW, cx, y - 1)) cy = y - 1;
-        else cair = 1;
-      } else if (cair == 1) {
-        cair = 0;
-      } else if (smb_movable(col, H, LW, cx, y + 1)) {
-        cy = y + 1;
-      }
-      nodes[nn] = smb_pack(cx, cy, cair, cj, a, cur, depth + 1);
-      smb_heap_push(heap, hn, ((uint32_t)((ex - cx) + balance * (depth + 1)) << 17) | (uint32_t)nn);
-      nn++;
     }
   }
   iterations = it;
@@ -253,28 +306,12 @@ __device__ inline void smb_scan_level(SmbLds &L, int H, int W, SmbResult &r) {
   r.stats[4] = smb_wave_sum(noise);
 }
 
-// The play half: the A* play-through of the level in L.col (smb_scan_level left it there) into r.stats[5..8] and the play record.
-// nodes / heap: this level's workspace slot.  Every lane returns with the same values.
-__device__ inline void smb_play_level(SmbLds &L, int H, int W, int power, uint2 *nodes, uint32_t *heap, const SmbPlayOut &out,
-                                      SmbResult &r) {
+// What a finished play-through leaves: the chain of its final node `fin` gives r.stats[5..8] (jumps, jumps-dist, dist-win,
+// sol-length) and the play record in `out` (empty: nothing is written).  fin, it1 and it2 are lane 0's values, `won` every
+// lane's.  Every lane returns with the same values.
+__device__ __forceinline__ void smb_play_result(int W, const uint2 *nodes, uint32_t fin, int won, int it1, int it2,
+                                                const SmbPlayOut &out, SmbResult &r) {
   const int lane = threadIdx.x & 63;
-  uint32_t fin = 0;
-  int it1 = 0, it2 = 0, won = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    for (int i = lane; i < SMB_SEEN_WORDS; i += 64) L.seen[i] = 0;
-    __syncthreads();
-    if (lane == 0) {
-      bool w;
-      int it;
-      fin = smb_search(L.col, L.seen, nodes, heap, H, W, power, pass == 0 ? 1 : 0, it, w);
-      won = w ? 1 : 0;
-      if (pass == 0) it1 = it;
-      else it2 = it;
-    }
-    won = __shfl(won, 0, 64);
-    __syncthreads();
-    if (won) break;
-  }
   // the final node's chain, by lane 0
   int fx = 0, fy = 0, fair = 0, fj = 0, fdepth = 0, jdist = 0;
   if (lane == 0) {
@@ -318,6 +355,31 @@ __device__ inline void smb_play_level(SmbLds &L, int H, int W, int power, uint2 
     }
 }
 
+// The play half: the A* play-through of the level in L.col (smb_scan_level left it there) into r.stats[5..8] and the play record.
+// nodes / heap: this level's workspace slot.  Every lane returns with the same values.
+__device__ inline void smb_play_level(SmbLds &L, int H, int W, int power, uint2 *nodes, uint32_t *heap, const SmbPlayOut &out,
+                                      SmbResult &r) {
+  const int lane = threadIdx.x & 63;
+  uint32_t fin = 0;
+  int it1 = 0, it2 = 0, won = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    for (int i = lane; i < SMB_SEEN_WORDS; i += 64) L.seen[i] = 0;
+    __syncthreads();
+    if (lane == 0) {
+      bool w;
+      int it;
+      fin = smb_search(L.col, L.seen, nodes, heap, H, W, power, pass == 0 ? 1 : 0, it, w);
+      won = w ? 1 : 0;
+      if (pass == 0) it1 = it;
+      else it2 = it;
+    }
+    won = __shfl(won, 0, 64);
+    __syncthreads();
+    if (won) break;
+  }
+  smb_play_result(W, nodes, fin, won, it1, it2, out, r);
+}
+
 // One level, by one 64-lane wave: the nine statistics and the play-through of the map in L.map ([H][W], ids 0..6).
 // nodes / heap: this level's workspace slot.  Every lane returns with the same SmbResult.
 __device__ inline void smb_evaluate_level(SmbLds &L, int H, int W, int power, uint2 *nodes, uint32_t *heap, const SmbPlayOut &out,
@@ -333,16 +395,9 @@ __global__ __launch_bounds__(64) void smb_kernel(const SmbArgs a) {
   if (lvl >= a.n) return;
   const int H = a.h, W = a.w, cells = H * W;
   const uint8_t *g = a.grids + (size_t)lvl * cells;
-  uint32_t err = 0;
-  for (int i = lane; i < cells; i += 64) {
-    uint8_t t = g[i];
-    if (t > 6) {
-      t = 0;
-      err = 1;
-    }
-    L.map[i] = t;
-  }
-  err = __any(err) ? 1u : 0u;
+  bool bad = false;
+  for (int i = lane; i < cells; i += 64) L.map[i] = smb_tile(g[i], bad);
+  const uint32_t err = __any(bad) ? 1u : 0u;
   __syncthreads();
   uint8_t *slot = a.ws + (size_t)lvl * a.ws_stride;
   uint2 *nodes = (uint2 *)slot;
@@ -358,14 +413,11 @@ __global__ __launch_bounds__(64) void smb_kernel(const SmbArgs a) {
 #pragma unroll
     for (int k = 0; k < SMB_STATS; k++) a.stats[(size_t)lvl * SMB_STATS + k] = r.stats[k];
     if (a.loss) {
-      // ControlWrapper.get_loss: the metrics in order, loss += -(distance to the target interval) * weight
+      // smb_target_loss as a loop: unrolled, the targets' 63 argument words are live at once, and at 106 scalar registers
+      // instead of 76 a SIMD holds six of this kernel's waves, not eight
       double loss = 0.0;
-      for (int k = 0; k < SMB_STATS; k++) {
-        if (!a.has_trg[k]) continue;
-        const double v = (double)r.stats[k];
-        const double d = v < a.trg_lo[k] ? a.trg_lo[k] - v : (v > a.trg_hi[k] ? v - a.trg_hi[k] : 0.0);
-        loss += -d * a.weight[k];
-      }
+      for (int k = 0; k < SMB_STATS; k++)
+        if (a.has_trg[k]) loss = loss + smb_target_term(r.stats[k], a.trg_lo[k], a.trg_hi[k], a.weight[k]);
       a.loss[lvl] = loss;
     }
     if (a.length) a.length[lvl] = r.length;

@@ -13,8 +13,7 @@
 //   take      at a reset, before the new level's last_loss: lane j < n_ctrl takes control j's queued triple (if the queue names
 //             it) or its resampled target, and writes it to LDS and to the record; lane 0 stores the flag word.  One commit per
 //             reset; the LDS copy is what the rest of the launch reads, so a rollout never reads its own stores back.
-//   loss      terms in the statistics' order, each -(d) * w rounded to double and then added, no fused multiply-add: the device
-//             equals the Python rules bit for bit whatever the targets.
+//   loss      smb_target_loss of smb/pcgrl_smb.h, the one every loss goes through, against the LDS copy of the targets.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,19 +143,10 @@ __device__ inline void smb_ctrl_take(SmbCtrlLds &C, const SmbCtrlArgs &c, int en
 }
 __device__ __forceinline__ void smb_ctrl_take(SmbCtrlNone &, const SmbCtrlArgs &, int, int) {}
 
-// ControlWrapper.get_loss with the env's own targets; the engine's sum: the statistics in order, -(d) * w rounded, then added
-__device__ inline double smb_ctrl_loss(const SmbCtrlLds &C, const int32_t *has_trg, const double *weight, const int32_t *stats) {
-#pragma clang fp contract(off)
-  double loss = 0.0;
-#pragma unroll
-  for (int k = 0; k < SMB_STATS; k++) {
-    if (!has_trg[k]) continue;
-    const double v = (double)stats[k], lo = C.v[k], hi = C.v[SMB_STATS + k];
-    const double d = v < lo ? lo - v : (v > hi ? v - hi : 0.0);
-    const double term = -d * weight[k];
-    loss = loss + term;
-  }
-  return loss;
+// ControlWrapper.get_loss with the env's own targets
+__device__ __forceinline__ double smb_ctrl_loss(const SmbCtrlLds &C, const int32_t *has_trg, const double *weight,
+                                                const int32_t *stats) {
+  return smb_target_loss(has_trg, weight, C.v, C.v + SMB_STATS, stats);
 }
 
 // control_wrappers.py:189-214: (target / range, metric / range) per control, as float32; lanes j < n_ctrl write

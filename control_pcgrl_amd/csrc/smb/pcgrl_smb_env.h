@@ -8,6 +8,10 @@
 //   step      load -> action -> statistics -> loss, reward, done -> latch the finished episode -> (auto_reset) draw the next map
 //             -> observation -> state.  The observation depends on the map and the position only, so its stores are issued
 //             BEFORE the search and drain under it; at an automatic reset they follow the new map's draw instead.
+//   pieces    the rules of a step and of a reset stand once, as device functions (smb_env_bad_action, _update, _restat, _emit,
+//             _latch, _inject, _reset_map, _commit_reset): the kernels below, the asynchronous ones (smb/pcgrl_smb_ready.h), the
+//             rollout (smb/pcgrl_smb_rollout.h) and the state set (smb/pcgrl_smb_state.h) compose them, each in its own order.
+//             DESIGN.md section 25 has the orders and the deliberate differences.
 //   shortcuts both exact: (1) the written tile equals the old one -> the statistics stay (the reference's own rule,
 //             pcgrl_env.py:314); (2) the tile changes but the cell's solidity (solid, brick, question, tube against the rest)
 //             does not -> the play-through's level is the same, so only the five map statistics are rescanned and jumps,
@@ -28,8 +32,6 @@
 #include "pcgrl_smb_ctrl.h"
 
 namespace pcgrl {
-
-constexpr int SMB_TILES = 7;
 
 struct alignas(16) SmbEnvState {
   int32_t pos[2];
@@ -97,17 +99,9 @@ namespace pcgrl {
 
 __device__ __forceinline__ bool smb_tile_solid(int t) { return t == 1 || t == 3 || t == 4 || t == 6; }
 
-// ControlWrapper.get_loss: the metrics in order, loss += -(distance to the target interval) * weight
-__device__ inline double smb_env_loss(const SmbEnvArgs &a, const int32_t *stats) {
-  double loss = 0.0;
-#pragma unroll
-  for (int k = 0; k < SMB_STATS; k++) {
-    if (!a.has_trg[k]) continue;
-    const double v = (double)stats[k];
-    const double d = v < a.trg_lo[k] ? a.trg_lo[k] - v : (v > a.trg_hi[k] ? v - a.trg_hi[k] : 0.0);
-    loss += -d * a.weight[k];
-  }
-  return loss;
+// ControlWrapper.get_loss against the handle's static targets
+__device__ __forceinline__ double smb_env_loss(const SmbEnvArgs &a, const int32_t *stats) {
+  return smb_target_loss(a.has_trg, a.weight, a.trg_lo, a.trg_hi, stats);
 }
 // the same against the targets a controllable launch holds in LDS (SmbCtrlNone: the static ones above)
 __device__ __forceinline__ double smb_env_loss(const SmbEnvArgs &a, const int32_t *stats, const SmbCtrlNone &) {
@@ -190,13 +184,19 @@ __device__ inline void smb_env_store_map(const SmbLds &L, const SmbEnvArgs &a, i
   for (int i = lane; i < a.map_stride / 16; i += 64) dst[i] = ((const uint4 *)L.map)[i];
 }
 
+// the env's workspace slot: the search's nodes, then its heap
+__device__ __forceinline__ uint2 *smb_env_nodes(const SmbEnvArgs &a, int env) {
+  return (uint2 *)(a.ws + (size_t)env * a.ws_stride);
+}
+__device__ __forceinline__ uint32_t *smb_env_heap(const SmbEnvArgs &a, int env) {
+  return (uint32_t *)(a.ws + (size_t)env * a.ws_stride + smb_nodes_per_pass(a.power) * 8);
+}
+
 // a fresh episode on the map in L.map: the search, the counters, last_loss (every lane holds the same S)
 template <class CtrlLds>
 __device__ inline void smb_env_begin(SmbLds &L, const SmbEnvArgs &a, int env, SmbEnvState &S, const int *pos, CtrlLds &C) {
-  uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
-  SmbPlayOut out = {nullptr, nullptr, 0, 0};
   SmbResult r;
-  smb_evaluate_level(L, a.h, a.w, a.power, (uint2 *)slot, (uint32_t *)(slot + smb_nodes_per_pass(a.power) * 8), out, r);
+  smb_evaluate_level(L, a.h, a.w, a.power, smb_env_nodes(a, env), smb_env_heap(a, env), SmbPlayOut{nullptr, nullptr, 0, 0}, r);
 #pragma unroll
   for (int k = 0; k < SMB_STATS; k++) S.stats[k] = r.stats[k];
   S.pos[0] = pos[0];
@@ -210,14 +210,167 @@ __device__ inline void smb_env_begin(SmbLds &L, const SmbEnvArgs &a, int env, Sm
   S.last_loss = smb_env_loss(a, S.stats, C);
 }
 
-#ifndef PCGRL_SMB_ENV_DEVICE_ONLY  // (smb/pcgrl_k_smb_ready.hip takes the device functions above without a second set of kernels)
+// ---- The pieces of a transition.  Every kernel that steps or resets an env -- smb_env_step_kernel and smb_env_reset_kernel below,
+// smb_ready_step_kernel and smb_ready_reset_kernel (smb/pcgrl_smb_ready.h), smb_env_rollout_kernel (smb/pcgrl_smb_rollout.h) and
+// smb_state_set_kernel (smb/pcgrl_smb_state.h) -- composes them in its own order; the rules stand here alone.  Every lane calls
+// them with the same S; `row` is the row of the per-step outputs (env, or k * n + env in a rollout).
+
+// the four per-row outputs of a step, by lane 0
+__device__ __forceinline__ void smb_env_write_row(const SmbEnvArgs &a, size_t row, int lane, double reward, bool done,
+                                                  const int32_t *stats) {
+  if (lane != 0) return;
+  if (a.reward) a.reward[row] = (float)reward;
+  if (a.reward64) a.reward64[row] = reward;
+  if (a.done) a.done[row] = done ? 1 : 0;
+  if (a.stats_out)
+    for (int k = 0; k < SMB_STATS; k++) a.stats_out[row * SMB_STATS + k] = stats[k];
+}
+
+// an action outside the space (pcgrl_step's rule): error bit 0, reward 0, not done, the same statistics, the env as it was.
+// The observation (and a ready step's status) is the caller's.
+__device__ __forceinline__ bool smb_env_bad_action(const SmbEnvArgs &a, int act, int n_act, size_t row, int lane,
+                                                   const SmbEnvState &S) {
+  if (act >= 0 && act < n_act) return false;
+  if (lane == 0) atomicOr(a.err, 1);
+  smb_env_write_row(a, row, lane, 0.0, false, S.stats);
+  return true;
+}
+
+// what the representation's update leaves beside the counters in S
+struct SmbEnvEdit {
+  int pos[2];             // the position after the update (committed by smb_env_emit)
+  bool changed, resolid;  // the written tile differs from the old one; the cell's solidity differs
+  bool done;
+};
+
+// the representation's update (narrow_rep.py:89-102, turtle_rep.py:87-107) on the map in L.map, the counters and done
+// (pcgrl_env.py:307-309).  A written tile is stored by lane 0 between two barriers.
+__device__ __forceinline__ SmbEnvEdit smb_env_update(SmbLds &L, const SmbEnvArgs &a, int act, int lane, SmbEnvState &S) {
+  const int H = a.h, W = a.w;
+  SmbEnvEdit e = {{S.pos[0], S.pos[1]}, false, false, false};
+  int tile = -1;
+  if (a.rep == PCGRL_REP_NARROW) {
+    tile = act;
+  } else if (act < 4) {
+    const int dr = act == 0 ? -1 : (act == 1 ? 1 : 0), dc = act == 2 ? -1 : (act == 3 ? 1 : 0);
+    e.pos[0] = min(max(e.pos[0] + dr, 0), H - 1);
+    e.pos[1] = min(max(e.pos[1] + dc, 0), W - 1);
+  } else {
+    tile = act - 4;
+  }
+  if (tile >= 0) {
+    const int idx = e.pos[0] * W + e.pos[1];
+    const int old = L.map[idx];
+    e.changed = old != tile;
+    e.resolid = smb_tile_solid(old) != smb_tile_solid(tile);
+    __syncthreads();
+    if (lane == 0) L.map[idx] = (uint8_t)tile;
+    __syncthreads();
+  }
+  if (a.rep == PCGRL_REP_NARROW) {  // the position the NEXT update writes: cell n_step mod cells, then n_step + 1
+    const int c = S.n_step % (H * W);
+    e.pos[0] = c / W;
+    e.pos[1] = c % W;
+    S.n_step++;
+  }
+  S.iteration++;
+  S.changes += e.changed ? 1 : 0;
+  S.ep_len++;
+  e.done = S.iteration > a.max_iterations;
+  if (a.max_changes >= 0) e.done = e.done || S.changes > a.max_changes;
+  return e;
+}
+
+// the statistics of the edited map in L.map by the two exact shortcuts, the search run to its end: the five map statistics, and
+// the play-through's four where the edit changed the level's solidity
+__device__ __forceinline__ void smb_env_restat(SmbLds &L, const SmbEnvArgs &a, int env, bool resolid, SmbEnvState &S) {
+  SmbResult r;
+  smb_scan_level(L, a.h, a.w, r);
+#pragma unroll
+  for (int k = 0; k < 5; k++) S.stats[k] = r.stats[k];
+  if (!resolid) return;
+  smb_play_level(L, a.h, a.w, a.power, smb_env_nodes(a, env), smb_env_heap(a, env), SmbPlayOut{nullptr, nullptr, 0, 0}, r);
+#pragma unroll
+  for (int k = 5; k < SMB_STATS; k++) S.stats[k] = r.stats[k];
+  S.searches++;
+  S.iters_total += r.it1 + r.it2;
+  S.iters_max = max(S.iters_max, r.it1 + r.it2);
+}
+
+// loss and reward (control_wrappers.py:227-229) of the step that left S.stats, the new position, and the step's output row
+template <class CtrlLds>
+__device__ __forceinline__ void smb_env_emit(const SmbEnvArgs &a, size_t row, int lane, const SmbEnvEdit &e, SmbEnvState &S,
+                                             const CtrlLds &C) {
+  const double loss = smb_env_loss(a, S.stats, C);
+  const double reward = loss - S.last_loss;
+  S.last_loss = loss;
+  S.ep_return += reward;
+  S.pos[0] = e.pos[0];
+  S.pos[1] = e.pos[1];
+  smb_env_write_row(a, row, lane, reward, e.done, S.stats);
+}
+
+// the latch of the finished episode
+__device__ __forceinline__ void smb_env_latch(SmbEnvState &S) {
+  S.last_return = S.ep_return;
+  S.last_len = S.ep_len;
+  S.last_count++;
+#pragma unroll
+  for (int k = 0; k < SMB_STATS; k++) S.last_stats[k] = S.stats[k];
+}
+
+// a caller's map into L.map: the padding of the stored row zeroed, the tile rule, error bit 1
+__device__ __forceinline__ void smb_env_clear_padding(SmbLds &L, const SmbEnvArgs &a, int lane) {
+  for (int i = a.h * a.w + lane; i < a.map_stride; i += 64) L.map[i] = 0;
+}
+__device__ __forceinline__ void smb_env_inject(SmbLds &L, const SmbEnvArgs &a, int env, int lane) {
+  const int cells = a.h * a.w;
+  smb_env_clear_padding(L, a, lane);
+  const uint8_t *g = a.init_grids + (size_t)env * cells;
+  bool bad = false;
+  for (int i = lane; i < cells; i += 64) L.map[i] = smb_tile(g[i], bad);
+  if (__any(bad) && lane == 0) atomicOr(a.err, 2);
+}
+
+// a reset's map into L.map and its start into pos: injected (it draws nothing, as pcgrl_reset does; init_pos clamped) or drawn
+__device__ __forceinline__ void smb_env_reset_map(SmbLds &L, const SmbEnvArgs &a, int env, int lane, int *pos) {
+  if (!a.init_grids) {
+    smb_env_clear_padding(L, a, lane);
+    smb_env_draw(L, a, env, lane, pos);
+    return;
+  }
+  smb_env_inject(L, a, env, lane);
+  pos[0] = pos[1] = 0;
+  if (a.init_pos && a.rep == PCGRL_REP_TURTLE) {
+    pos[0] = min(max(a.init_pos[(size_t)env * 2], 0), a.h - 1);
+    pos[1] = min(max(a.init_pos[(size_t)env * 2 + 1], 0), a.w - 1);
+  }
+}
+
+// What a reset writes back (lane 0): only the fields it owns -- the last finished episode stays where it is -- and the search's
+// (searches, last_loss, the statistics) only when the search is over: pending statistics keep the old ones until then.
+__device__ __forceinline__ void smb_env_commit_reset(SmbEnvState *P, const SmbEnvState &S, bool finished) {
+  P->pos[0] = S.pos[0];
+  P->pos[1] = S.pos[1];
+  P->n_step = P->iteration = P->changes = P->ep_len = 0;
+  P->iters_total = S.iters_total;
+  P->iters_max = S.iters_max;
+  P->ep_return = 0.0;
+  if (!finished) return;
+  P->searches = S.searches;
+  P->last_loss = S.last_loss;
+#pragma unroll
+  for (int k = 0; k < SMB_STATS; k++) P->stats[k] = S.stats[k];
+}
+
+
+#ifndef PCGRL_SMB_ENV_DEVICE_ONLY  // (smb/pcgrl_k_smb_ready.hip composes the pieces above without a second set of kernels)
 template <bool CTRL>
 __global__ __launch_bounds__(64) void smb_env_reset_kernel(const SmbEnvArgs a) {
   __shared__ SmbLds L;
   __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
-  const int H = a.h, W = a.w, cells = H * W;
   const bool active = !a.mask || a.mask[env] != 0;
   SmbEnvState *P = a.st + env;
   smb_ctrl_load(C, a.ctrl, env, lane);
@@ -233,44 +386,13 @@ __global__ __launch_bounds__(64) void smb_env_reset_kernel(const SmbEnvArgs a) {
     if constexpr (CTRL) smb_ctrl_write_obs(C, a.ctrl, env, lane, P->stats);
     return;
   }
-  for (int i = cells + lane; i < a.map_stride; i += 64) L.map[i] = 0;  // the padding of the stored row
-  if (a.init_grids) {  // an injected map draws nothing, as pcgrl_reset does
-    const uint8_t *g = a.init_grids + (size_t)env * cells;
-    bool bad = false;
-    for (int i = lane; i < cells; i += 64) {
-      uint8_t t = g[i];
-      if (t >= SMB_TILES) {
-        t = 0;
-        bad = true;
-      }
-      L.map[i] = t;
-    }
-    if (__any(bad) && lane == 0) atomicOr(a.err, 2);
-    pos[0] = pos[1] = 0;
-    if (a.init_pos && a.rep == PCGRL_REP_TURTLE) {
-      pos[0] = min(max(a.init_pos[(size_t)env * 2], 0), H - 1);
-      pos[1] = min(max(a.init_pos[(size_t)env * 2 + 1], 0), W - 1);
-    }
-  } else {
-    smb_env_draw(L, a, env, lane, pos);
-  }
+  smb_env_reset_map(L, a, env, lane, pos);
   __syncthreads();
   smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
   smb_env_store_map(L, a, env, lane);
   smb_env_begin(L, a, env, S, pos, C);
   smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
-  if (lane == 0) {
-    P->pos[0] = S.pos[0];
-    P->pos[1] = S.pos[1];
-    P->n_step = P->iteration = P->changes = P->ep_len = 0;
-    P->searches = S.searches;
-    P->iters_total = S.iters_total;
-    P->iters_max = S.iters_max;
-    P->ep_return = 0.0;
-    P->last_loss = S.last_loss;
-#pragma unroll
-    for (int k = 0; k < SMB_STATS; k++) P->stats[k] = S.stats[k];
-  }
+  if (lane == 0) smb_env_commit_reset(P, S, true);
 }
 
 __global__ __launch_bounds__(64) void smb_env_observe_kernel(const SmbEnvArgs a) {
@@ -288,105 +410,32 @@ __global__ __launch_bounds__(64) void smb_env_step_kernel(const SmbEnvArgs a) {
   __shared__ typename SmbCtrlLdsOf<CTRL>::type C;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
-  const int H = a.h, W = a.w, cells = H * W;
   smb_env_load_map(L, a, env, lane);
   SmbEnvState S = a.st[env];
   smb_ctrl_load(C, a.ctrl, env, lane);
   const int act = a.actions[env];
-  const int n_act = a.rep == PCGRL_REP_NARROW ? SMB_TILES : 4 + SMB_TILES;
   __syncthreads();
-  if (act < 0 || act >= n_act) {  // pcgrl_step's rule: the error bit, and the env as it was
-    if (lane == 0) {
-      atomicOr(a.err, 1);
-      if (a.reward) a.reward[env] = 0.0f;
-      if (a.reward64) a.reward64[env] = 0.0;
-      if (a.done) a.done[env] = 0;
-      if (a.stats_out)
-        for (int k = 0; k < SMB_STATS; k++) a.stats_out[(size_t)env * SMB_STATS + k] = S.stats[k];
-    }
+  if (smb_env_bad_action(a, act, a.rep == PCGRL_REP_NARROW ? SMB_TILES : 4 + SMB_TILES, env, lane, S)) {
     smb_env_write_obs(L, a, env, lane, S.pos[0], S.pos[1]);
     smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);
     return;
   }
-  // the representation's update (narrow_rep.py:89-102, turtle_rep.py:87-107)
-  int pos[2] = {S.pos[0], S.pos[1]};
-  int tile = -1;
-  if (a.rep == PCGRL_REP_NARROW) {
-    tile = act;
-  } else if (act < 4) {
-    const int dr = act == 0 ? -1 : (act == 1 ? 1 : 0), dc = act == 2 ? -1 : (act == 3 ? 1 : 0);
-    pos[0] = min(max(pos[0] + dr, 0), H - 1);
-    pos[1] = min(max(pos[1] + dc, 0), W - 1);
-  } else {
-    tile = act - 4;
+  SmbEnvEdit e = smb_env_update(L, a, act, lane, S);
+  const bool renew = e.done && a.auto_reset != 0;
+  if (!renew) smb_env_write_obs(L, a, env, lane, e.pos[0], e.pos[1]);  // drains under the search
+  if (e.changed) {
+    smb_env_store_map(L, a, env, lane);  // before the search: a synchronous step always ends in this launch
+    smb_env_restat(L, a, env, e.resolid, S);
   }
-  bool changed = false, resolid = false;
-  if (tile >= 0) {
-    const int idx = pos[0] * W + pos[1];
-    const int old = L.map[idx];
-    changed = old != tile;
-    resolid = smb_tile_solid(old) != smb_tile_solid(tile);
-    __syncthreads();
-    if (lane == 0) L.map[idx] = (uint8_t)tile;
-    __syncthreads();
-  }
-  if (a.rep == PCGRL_REP_NARROW) {  // the position the NEXT update writes: cell n_step mod cells, then n_step + 1
-    const int c = S.n_step % cells;
-    pos[0] = c / W;
-    pos[1] = c % W;
-    S.n_step++;
-  }
-  S.iteration++;
-  S.changes += changed ? 1 : 0;
-  S.ep_len++;
-  bool done = S.iteration > a.max_iterations;  // pcgrl_env.py:307-309
-  if (a.max_changes >= 0) done = done || S.changes > a.max_changes;
-  const bool renew = done && a.auto_reset != 0;
-  if (!renew) smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);  // drains under the search
-  if (changed) {
-    smb_env_store_map(L, a, env, lane);
-    SmbResult r;
-    smb_scan_level(L, H, W, r);
-#pragma unroll
-    for (int k = 0; k < 5; k++) S.stats[k] = r.stats[k];
-    if (resolid) {
-      uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
-      SmbPlayOut out = {nullptr, nullptr, 0, 0};
-      smb_play_level(L, H, W, a.power, (uint2 *)slot, (uint32_t *)(slot + smb_nodes_per_pass(a.power) * 8), out, r);
-#pragma unroll
-      for (int k = 5; k < SMB_STATS; k++) S.stats[k] = r.stats[k];
-      S.searches++;
-      S.iters_total += r.it1 + r.it2;
-      S.iters_max = max(S.iters_max, r.it1 + r.it2);
-    }
-  }
-  const double loss = smb_env_loss(a, S.stats, C);
-  const double reward = loss - S.last_loss;  // control_wrappers.py:227-229
-  S.last_loss = loss;
-  S.ep_return += reward;
-  S.pos[0] = pos[0];
-  S.pos[1] = pos[1];
-  if (lane == 0) {
-    if (a.reward) a.reward[env] = (float)reward;
-    if (a.reward64) a.reward64[env] = reward;
-    if (a.done) a.done[env] = done ? 1 : 0;
-    if (a.stats_out)
-      for (int k = 0; k < SMB_STATS; k++) a.stats_out[(size_t)env * SMB_STATS + k] = S.stats[k];
-  }
-  if (done) {
-    S.last_return = S.ep_return;
-    S.last_len = S.ep_len;
-    S.last_count++;
-#pragma unroll
-    for (int k = 0; k < SMB_STATS; k++) S.last_stats[k] = S.stats[k];
-  }
+  smb_env_emit(a, env, lane, e, S, C);
+  if (e.done) smb_env_latch(S);
   if (renew) {  // the next episode inside the same launch: the observation returned is its first
     __syncthreads();
-    smb_env_draw(L, a, env, lane, pos);
+    smb_env_draw(L, a, env, lane, e.pos);
     __syncthreads();
-    smb_env_write_obs(L, a, env, lane, pos[0], pos[1]);
+    smb_env_write_obs(L, a, env, lane, e.pos[0], e.pos[1]);
     smb_env_store_map(L, a, env, lane);
-    smb_env_begin(L, a, env, S, pos, C);
+    smb_env_begin(L, a, env, S, e.pos, C);
   }
   smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);  // the new episode's, where the step began one
   if (lane == 0) a.st[env] = S;

@@ -3,9 +3,10 @@
 //
 // smb_env_rollout_kernel keeps smb_env_step_kernel's layout (smb/pcgrl_smb_env.h): one 64-lane wave per env, the map in SmbLds.
 //   once      the map and the SmbEnvState record are loaded; with drawn actions the handle's draw counter is read.
-//   per step  exactly smb_env_step_kernel's step on the record in registers and the map in LDS -- the action check, the update,
-//             the two exact shortcuts, loss and float64 reward, done, the latch of the finished episode and, with auto_reset,
-//             the next episode drawn and searched inside the same iteration -- and row k of reward / reward64 / done / stats.
+//   per step  the pieces smb_env_step_kernel composes (smb_env_bad_action, _update, _restat, _emit, _latch, _begin), in the same
+//             order, on the record in registers and the map in LDS -- the action check, the update, the two exact shortcuts,
+//             loss and float64 reward, done, the latch of the finished episode and, with auto_reset, the next episode drawn and
+//             searched inside the same iteration -- with row k of reward / reward64 / done / stats as the output row.
 //             A launch therefore lasts as long as the largest, over envs, of the env's OWN K steps, not as the sum over steps
 //             of the batch's longest search.
 //   at the end  the map (if an edit or a new episode touched it) and the record.  The two PCG64 streams stay in HBM between the
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(64) void smb_env_rollout_kernel(const SmbRolloutArg
   const SmbEnvArgs &a = ra.e;
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= a.n) return;
-  const int H = a.h, W = a.w, cells = H * W, N = a.n, K = ra.n_steps;
+  const int N = a.n, K = ra.n_steps;
   smb_env_load_map(L, a, env, lane);
   SmbEnvState S = a.st[env];
   smb_ctrl_load(C, a.ctrl, env, lane);
@@ -112,89 +113,20 @@ __global__ __launch_bounds__(64) void smb_env_rollout_kernel(const SmbRolloutArg
     if (ra.actions_out && lane == 0) ra.actions_out[row] = act;
     const bool want_obs = ra.obs_mode == 2 || (ra.obs_mode == 1 && k == K - 1);
     const int obs_row = ra.obs_mode == 2 ? (int)row : env;
-    if (act < 0 || act >= ra.n_actions) {  // pcgrl_smb_env_step's rule: the error bit, and the env as it was
-      if (lane == 0) {
-        atomicOr(a.err, 1);
-        if (a.reward) a.reward[row] = 0.0f;
-        if (a.reward64) a.reward64[row] = 0.0;
-        if (a.done) a.done[row] = 0;
-        if (a.stats_out)
-          for (int j = 0; j < SMB_STATS; j++) a.stats_out[row * SMB_STATS + j] = S.stats[j];
-      }
+    if (smb_env_bad_action(a, act, ra.n_actions, row, lane, S)) {  // the env as it was; the loop goes on
       if (want_obs) smb_env_write_obs(L, a, obs_row, lane, S.pos[0], S.pos[1]);
       continue;
     }
-    // the representation's update (narrow_rep.py:89-102, turtle_rep.py:87-107)
-    int pos[2] = {S.pos[0], S.pos[1]};
-    int tile = -1;
-    if (a.rep == PCGRL_REP_NARROW) {
-      tile = act;
-    } else if (act < 4) {
-      const int dr = act == 0 ? -1 : (act == 1 ? 1 : 0), dc = act == 2 ? -1 : (act == 3 ? 1 : 0);
-      pos[0] = min(max(pos[0] + dr, 0), H - 1);
-      pos[1] = min(max(pos[1] + dc, 0), W - 1);
-    } else {
-      tile = act - 4;
-    }
-    bool changed = false, resolid = false;
-    if (tile >= 0) {
-      const int idx = pos[0] * W + pos[1];
-      const int old = L.map[idx];
-      changed = old != tile;
-      resolid = smb_tile_solid(old) != smb_tile_solid(tile);
-      __syncthreads();
-      if (lane == 0) L.map[idx] = (uint8_t)tile;
-      __syncthreads();
-    }
-    if (a.rep == PCGRL_REP_NARROW) {  // the position the NEXT update writes: cell n_step mod cells, then n_step + 1
-      const int c = S.n_step % cells;
-      pos[0] = c / W;
-      pos[1] = c % W;
-      S.n_step++;
-    }
-    S.iteration++;
-    S.changes += changed ? 1 : 0;
-    S.ep_len++;
-    bool done = S.iteration > a.max_iterations;  // pcgrl_env.py:307-309
-    if (a.max_changes >= 0) done = done || S.changes > a.max_changes;
-    const bool renew = done && a.auto_reset != 0;
-    if (want_obs && !renew) smb_env_write_obs(L, a, obs_row, lane, pos[0], pos[1]);  // drains under the search
-    if (changed) {
+    SmbEnvEdit e = smb_env_update(L, a, act, lane, S);
+    const bool renew = e.done && a.auto_reset != 0;
+    if (want_obs && !renew) smb_env_write_obs(L, a, obs_row, lane, e.pos[0], e.pos[1]);  // drains under the search
+    if (e.changed) {
       dirty = true;
-      SmbResult r;
-      smb_scan_level(L, H, W, r);
-#pragma unroll
-      for (int j = 0; j < 5; j++) S.stats[j] = r.stats[j];
-      if (resolid) {
-        uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
-        SmbPlayOut out = {nullptr, nullptr, 0, 0};
-        smb_play_level(L, H, W, a.power, (uint2 *)slot, (uint32_t *)(slot + smb_nodes_per_pass(a.power) * 8), out, r);
-#pragma unroll
-        for (int j = 5; j < SMB_STATS; j++) S.stats[j] = r.stats[j];
-        S.searches++;
-        S.iters_total += r.it1 + r.it2;
-        S.iters_max = max(S.iters_max, r.it1 + r.it2);
-      }
+      smb_env_restat(L, a, env, e.resolid, S);
     }
-    const double loss = smb_env_loss(a, S.stats, C);
-    const double reward = loss - S.last_loss;  // control_wrappers.py:227-229
-    S.last_loss = loss;
-    S.ep_return += reward;
-    S.pos[0] = pos[0];
-    S.pos[1] = pos[1];
-    if (lane == 0) {
-      if (a.reward) a.reward[row] = (float)reward;
-      if (a.reward64) a.reward64[row] = reward;
-      if (a.done) a.done[row] = done ? 1 : 0;
-      if (a.stats_out)
-        for (int j = 0; j < SMB_STATS; j++) a.stats_out[row * SMB_STATS + j] = S.stats[j];
-    }
-    if (done) {
-      S.last_return = S.ep_return;
-      S.last_len = S.ep_len;
-      S.last_count++;
-#pragma unroll
-      for (int j = 0; j < SMB_STATS; j++) S.last_stats[j] = S.stats[j];
+    smb_env_emit(a, row, lane, e, S, C);
+    if (e.done) {
+      smb_env_latch(S);
       if (lane == 0) {  // lane 0 wrote the zeros above: its own stores, read back in program order
         if (ra.ep_count) ra.ep_count[env] += 1;
         if (ra.ep_return_sum) ra.ep_return_sum[env] += S.ep_return;
@@ -206,10 +138,10 @@ __global__ __launch_bounds__(64) void smb_env_rollout_kernel(const SmbRolloutArg
     if (renew) {  // the next episode inside the same iteration: the observation of this step is its first
       dirty = true;
       __syncthreads();
-      smb_env_draw(L, a, env, lane, pos);
+      smb_env_draw(L, a, env, lane, e.pos);
       __syncthreads();
-      if (want_obs) smb_env_write_obs(L, a, obs_row, lane, pos[0], pos[1]);
-      smb_env_begin(L, a, env, S, pos, C);
+      if (want_obs) smb_env_write_obs(L, a, obs_row, lane, e.pos[0], e.pos[1]);
+      smb_env_begin(L, a, env, S, e.pos, C);
     }
   }
   smb_ctrl_write_obs(C, a.ctrl, env, lane, S.stats);  // the control observation after the last step

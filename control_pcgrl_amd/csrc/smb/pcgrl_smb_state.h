@@ -12,8 +12,8 @@
 //             iters_total goes out WITHOUT the iterations its parked search has spent so far: that search is not in the image
 //             and runs again from iteration 0 after an import, which counts them a second time.
 //   import    env j takes row index[j] of the image.  A busy row's search starts over: the import writes "parked after 0
-//             iterations" -- nodes[0], heap[0], a zeroed visited set and the loop's words as smb_play_budgeted starts them -- so
-//             the stepping kernels resume it as they resume any parked search, and their code is what it was.
+//             iterations" -- smb_search_start's nodes[0], heap[0] and loop words, and a zeroed visited set -- so the stepping
+//             kernels resume it as they resume any parked search.
 //   set       the map, position, counters and return from the caller; the nine statistics and last_loss by the level's
 //             evaluation, under the budget where one is set (unfinished -> pending statistics, as a reset leaves them).
 //   controls  the image of a controllable env (smb/pcgrl_smb_ctrl.h) has a fifth section, the SmbCtrlRec records [n][448], on the
@@ -129,13 +129,12 @@ __global__ __launch_bounds__(64) void smb_state_import_kernel(const SmbStateArgs
     P->action = m.y;
   }
   if (m.x == SMB_READY_IDLE) return;  // whatever was parked here is abandoned, as a masked reset abandons it
-  // the row's search, parked after 0 iterations: what smb_play_budgeted writes when it starts one
+  // the row's search, parked after 0 iterations: a zeroed visited set and pass 1 as smb_play_budgeted starts it
   for (int i = lane; i < SMB_SEEN_WORDS; i += 64) P->seen[i] = 0;
   if (lane == 0) {
-    P->pass = 0, P->it = 0, P->nn = 1, P->hn = 1, P->best = 0, P->best_x = -1, P->best_depth = 0, P->it1 = 0;
-    uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
-    ((uint2 *)slot)[0] = smb_pack(1, a.h - 3, 0, 0, 0, SMB_NO_PARENT, 0);
-    ((uint32_t *)(slot + smb_nodes_per_pass(a.power) * 8))[0] = (uint32_t)(a.w + 4 - 1) << 17;
+    P->pass = 0, P->it1 = 0;
+    smb_search_start(smb_env_nodes(a, env), smb_env_heap(a, env), a.h, a.w, true, P->it, P->nn, P->hn, P->best, P->best_x,
+                     P->best_depth);
   }
 }
 
@@ -148,19 +147,8 @@ __global__ __launch_bounds__(64) void smb_state_set_kernel(const SmbStateArgs sa
   if (env >= a.n) return;
   if (a.mask && a.mask[env] == 0) return;
   smb_ctrl_load(C, a.ctrl, env, lane);  // the active targets: setting a state is no reset and takes nothing from the queue
-  const int H = a.h, W = a.w, cells = H * W;
-  for (int i = cells + lane; i < a.map_stride; i += 64) L.map[i] = 0;  // the padding of the stored row
-  const uint8_t *g = a.init_grids + (size_t)env * cells;
-  bool bad = false;
-  for (int i = lane; i < cells; i += 64) {
-    uint8_t t = g[i];
-    if (t >= SMB_TILES) {
-      t = 0;
-      bad = true;
-    }
-    L.map[i] = t;
-  }
-  if (__any(bad) && lane == 0) atomicOr(a.err, 2);
+  const int H = a.h, W = a.w;
+  smb_env_inject(L, a, env, lane);
   __syncthreads();
   smb_env_store_map(L, a, env, lane);
   SmbEnvState *Q = a.st + env;
@@ -174,9 +162,8 @@ __global__ __launch_bounds__(64) void smb_state_set_kernel(const SmbStateArgs sa
   const int iteration = c ? c[0] : 0, changes = c ? c[1] : 0, n_step = c ? c[2] : 0;
   int searches = c ? c[3] : 0;
   const double ep_return = sa.ep_return ? sa.ep_return[env] : 0.0;
-  uint8_t *slot = a.ws + (size_t)env * a.ws_stride;
-  uint2 *nodes = (uint2 *)slot;
-  uint32_t *heap = (uint32_t *)(slot + smb_nodes_per_pass(a.power) * 8);
+  uint2 *nodes = smb_env_nodes(a, env);
+  uint32_t *heap = smb_env_heap(a, env);
   SmbResult r;
   bool finished = true;
   int spent;
