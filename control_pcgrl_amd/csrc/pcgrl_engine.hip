@@ -51,6 +51,8 @@
 #include "smb/pcgrl_smb_vector.h"  // the float32 hand-out (RLlib's Box form)
 #include "../../include/pcgrl_amd_smb_measures.h"
 #include "smb/pcgrl_smb_measures.h"  // level measures and pairwise Hamming diversity of smb maps
+#include "../../include/pcgrl_amd_loderunner.h"
+#include "loderunner/pcgrl_loderunner.h"  // Lode Runner levels: statistics, win score and gold searches
 
 using namespace pcgrl;
 
@@ -2185,6 +2187,55 @@ int pcgrl_smb_evaluate(const pcgrl_smb_config *cfg, int32_t n, const uint8_t *d_
     a.trg_hi[k] = cfg->trg_hi[k];
   }
   HIPCHK(launch_smb(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Lode Runner levels
+// include/pcgrl_amd_loderunner.h; kernel in loderunner/pcgrl_loderunner.h.  No handle, as for the Mario levels above.
+static int lr_check_shape(const char *who, int32_t h, int32_t w) {
+  if (h < 1 || h > LR_MAX_H || w < 1 || w > LR_MAX_W)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..16 rows and 1..32 columns only");
+  return PCGRL_OK;
+}
+
+int64_t pcgrl_loderunner_workspace_bytes(int32_t n, int32_t h, int32_t w) {
+  if (n < 1 || lr_check_shape("pcgrl_loderunner_workspace_bytes", h, w) != PCGRL_OK) return -1;
+  return (int64_t)lr_blocks(n, h, w) * lr_ws_stride(h, w);
+}
+
+int pcgrl_loderunner_evaluate(const pcgrl_loderunner_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
+                              int64_t workspace_bytes, int32_t gold_cap, double *d_stats, double *d_loss, int32_t *d_play,
+                              int8_t *d_gold_state, int16_t *d_gold_dist, uint32_t *d_error, void *stream) {
+  const char *who = "pcgrl_loderunner_evaluate";
+  if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (gold_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": gold_cap must not be negative");
+  const int rc = lr_check_shape(who, cfg->h, cfg->w);
+  if (rc != PCGRL_OK) return rc;
+  const int64_t stride = lr_ws_stride(cfg->h, cfg->w);
+  if (!d_workspace || ((uintptr_t)d_workspace & 3u) || workspace_bytes < (int64_t)lr_blocks(n, cfg->h, cfg->w) * stride)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 4-byte aligned or smaller than "
+                                                 "pcgrl_loderunner_workspace_bytes");
+  LrArgs a = {};
+  a.h = cfg->h;
+  a.w = cfg->w;
+  a.n = n;
+  a.grids = d_grids;
+  a.ws = (uint32_t *)d_workspace;
+  a.ws_stride = stride;
+  a.gold_cap = gold_cap;
+  a.stats = d_stats;
+  a.loss = d_loss;
+  a.play = d_play;
+  a.gold_state = d_gold_state;
+  a.gold_dist = d_gold_dist;
+  a.error = d_error;
+  for (int k = 0; k < LR_STATS; k++) {
+    a.has_trg[k] = cfg->has_trg[k];
+    a.weight[k] = cfg->weight[k];
+    a.trg_lo[k] = cfg->trg_lo[k];
+    a.trg_hi[k] = cfg->trg_hi[k];
+  }
+  HIPCHK(launch_loderunner(a, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

@@ -1,0 +1,158 @@
+"""Lode Runner levels on the device: the five statistics of LoderunnerProblem.get_stats, the loss ControlWrapper.get_loss
+would derive from them and the per-gold record of the gold searches behind `win` and `path-length`, for a batch of maps in one
+launch (include/pcgrl_amd_loderunner.h, csrc/loderunner/pcgrl_loderunner.h).
+
+This module evaluates maps; stepping Lode Runner environments is not built.  It is not part of the 2-D engine, so PROBLEMS /
+problem_spec / build_config do not know "loderunner".  file:line references are relative to the reference's
+control_pcgrl/envs/probs/ directory.
+
+The reference abandons an evaluation after one second of wall clock (loderunner/engine.py:254, 287, 293).  The device has no
+such limit: its result is the reference's with the clock stopped.  At the stock 8 x 12 the limit does not bite; above the stock
+size the reference's own answer depends on the host's speed.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from .problems import ProblemSpec, target_interval
+
+LODERUNNER_TILES = ["empty", "brick", "ladder", "rope", "solid", "gold", "enemy", "player"]  # loderunner_prob.py:46
+LODERUNNER_STAT_KEYS = ["player", "enemies", "gold", "win", "path-length"]
+MAX_H, MAX_W = 16, 32
+
+
+def loderunner_spec(map_shape=(8, 12)) -> ProblemSpec:
+    """loderunner_prob.py:13-14 sets _width = 12, _height = 8 BEFORE loderunner_ctrl_prob.py:20-44 derive the path-length
+    target and the bounds, so those are frozen at the stock size whatever the map."""
+    fw, fh = 12, 8
+    n = fw * fh
+    max_path = float((math.ceil(fw / 2) * fh + math.floor(fh / 2)) * 2 - 1)  # 103.0
+    weights = {"player": 1, "enemies": 0, "gold": 0, "win": 1, "path-length": 0}  # loderunner_prob.py:35-44 _reward_weights
+    return ProblemSpec(
+        "loderunner", list(LODERUNNER_TILES), list(LODERUNNER_STAT_KEYS),
+        {"player": 1, "enemies": 2, "gold": (1, 10), "win": 1, "path-length": max_path},
+        {"player": (0, n), "enemies": (0, n), "gold": (0, 10), "win": (0, 1), "path-length": (0, max_path)},
+        dict(weights), dict(weights),
+    )
+
+
+def loderunner_config(map_shape=(8, 12), weights=None) -> "_lib.PcgrlLoderunnerConfig":
+    """The C config of include/pcgrl_amd_loderunner.h: the frozen targets as zero-loss intervals, and the weights."""
+    spec = loderunner_spec(map_shape)
+    weights = dict(spec.default_weights) if weights is None else dict(weights)
+    unknown = set(weights) - set(spec.stat_keys)
+    if unknown:
+        raise ValueError(f"unknown loderunner statistics in weights: {sorted(unknown)}")
+    cfg = _lib.PcgrlLoderunnerConfig()
+    cfg.h, cfg.w = int(map_shape[0]), int(map_shape[1])
+    for i, k in enumerate(spec.stat_keys):
+        lo, hi = target_interval(spec.static_trgs[k])
+        cfg.has_trg[i] = 1
+        cfg.weight[i] = float(weights.get(k, 0.0))
+        cfg.trg_lo[i], cfg.trg_hi[i] = lo, hi
+    return cfg
+
+
+class LodeRunnerEvaluator:
+    """Evaluates batches of Lode Runner maps on one device.  Owns the search workspace, a torch tensor sized at the first
+    evaluate() for the launch it needs (pcgrl_loderunner_workspace_bytes(min(n, max_levels), H, W) bytes: one slot per block of
+    the launch -- 150 KiB per level at 8 x 12 up to 4096 levels, 598 MiB; never more than 640 MiB) and grown when a larger batch
+    comes; batches above max_levels run as successive launches on the current stream.  A call to be captured in a graph wants
+    one eager call of the same size before it, so that the capture allocates no workspace.  There is no wall-clock limit
+    (see the module docstring) and no CPU fallback."""
+
+    def __init__(self, map_shape=(8, 12), device="cuda:0", weights=None, max_levels=4096):
+        self._L = _lib.lib()
+        map_shape = tuple(int(s) for s in map_shape)
+        if len(map_shape) != 2:
+            raise ValueError(f"loderunner maps are 2-D, got shape {map_shape}")
+        if int(max_levels) < 1:
+            raise ValueError("max_levels must be at least 1")
+        self.map_shape = map_shape
+        self.spec = loderunner_spec(map_shape)
+        self.max_levels = int(max_levels)
+        self._cfg = loderunner_config(map_shape, weights)
+        nbytes = self._L.pcgrl_loderunner_workspace_bytes(self.max_levels, map_shape[0], map_shape[1])
+        if nbytes < 0:
+            raise NotImplementedError(f"loderunner: map_shape {map_shape} outside 1..{MAX_H} x 1..{MAX_W}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("LodeRunnerEvaluator needs a cuda device: there is no CPU fallback")
+        self._workspace, self._workspace_bytes, self._closed = None, 0, False  # sized by the first evaluate()
+        self._error = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def evaluate(self, grids, gold_cap=32):
+        """grids: uint8 [n][H][W] (a device tensor, or anything torch.as_tensor takes).  Returns device tensors: stats float64
+        [n][5] (spec.stat_keys order; win and path_length are views of its columns), loss float64 [n], play int32 [n][4]
+        (searched, landing row, landing column, golds collected including those on the starting fall), and with gold_cap > 0:
+        gold_state int8 [n][gold_cap] (per gold in row-major order 0 not collected, 1 by its own pair of searches, 2 on
+        another gold's path, 3 on the starting fall, -1 past the last gold) and gold_dist int16 [n][gold_cap] (what the gold
+        added to path-length).  The totals stay complete when gold_cap is smaller than the number of golds."""
+        if self._closed:
+            raise RuntimeError("LodeRunnerEvaluator is closed")
+        g = torch.as_tensor(grids, device=self.device)
+        if g.dtype != torch.uint8:
+            g = g.to(torch.uint8)
+        if g.dim() == 2:
+            g = g.unsqueeze(0)
+        if g.dim() != 3 or tuple(g.shape[1:]) != self.map_shape:
+            raise ValueError(f"grids must have shape [n]{list(self.map_shape)}, got {list(g.shape)}")
+        g = g.contiguous()
+        n = g.shape[0]
+        if n < 1:
+            raise ValueError("no levels to evaluate")
+        gold_cap = int(gold_cap)
+        if gold_cap < 0:
+            raise ValueError("gold_cap must not be negative")
+        dev = self.device
+        out = {"stats": torch.empty((n, 5), dtype=torch.float64, device=dev),
+               "loss": torch.empty(n, dtype=torch.float64, device=dev),
+               "play": torch.empty((n, 4), dtype=torch.int32, device=dev)}
+        if gold_cap > 0:
+            out["gold_state"] = torch.empty((n, gold_cap), dtype=torch.int8, device=dev)
+            out["gold_dist"] = torch.empty((n, gold_cap), dtype=torch.int16, device=dev)
+        err = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def ptr(name, lo):
+            return out[name][lo:].data_ptr() if name in out else None
+
+        with torch.cuda.device(dev):
+            stream = self._stream()
+            need = self._L.pcgrl_loderunner_workspace_bytes(min(n, self.max_levels), self.map_shape[0], self.map_shape[1])
+            if need > self._workspace_bytes:
+                if self._workspace is not None:  # launches already enqueued on this stream keep it until they are done
+                    self._workspace.record_stream(torch.cuda.current_stream(dev))
+                self._workspace = torch.empty(need // 4, dtype=torch.int32, device=dev)
+                self._workspace_bytes = need
+            for lo in range(0, n, self.max_levels):
+                m = min(self.max_levels, n - lo)
+                _lib.check(self._L.pcgrl_loderunner_evaluate(
+                    C.byref(self._cfg), m, g[lo:].data_ptr(), self._workspace.data_ptr(), self._workspace_bytes, gold_cap,
+                    ptr("stats", lo), ptr("loss", lo), ptr("play", lo), ptr("gold_state", lo), ptr("gold_dist", lo),
+                    err[lo:].data_ptr(), stream), "pcgrl_loderunner_evaluate")
+        self._error |= err.max()
+        out["error"] = err
+        out["win"] = out["stats"][:, 3]
+        out["path_length"] = out["stats"][:, 4]
+        return out
+
+    def check_errors(self):
+        """Raises if a launch since the last check read a tile id above 7 (it was taken as empty).  Synchronises."""
+        bits = int(self._error.item())
+        self._error.zero_()
+        if bits & 1:
+            raise ValueError("loderunner: a tile id above 7 was seen on the device (read as empty)")
+
+    def close(self):
+        self._workspace, self._workspace_bytes, self._closed = None, 0, True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
