@@ -15,7 +15,8 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   SmbVectorEnv             the same envs behind the VectorEnv call shape, the float32 Box image written once by a kernel of
                            its own; make_vector_env(cfg, n) picks SmbVectorEnv or PcgrlVectorEnv by problem
   LodeRunnerEvaluator      Lode Runner levels: the five statistics, the loss and the per-gold record of the gold searches of a
-                           batch of maps in one launch (loderunner_spec() has the problem's tables)
+                           batch of maps in one launch (loderunner_spec() has the problem's tables); measures(), diversity()
+                           and behaviour(): the behaviour vector under the names of LODERUNNER_BC_NAMES
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of
@@ -31,6 +32,6 @@ from .smb import SmbEvaluator, smb_spec  # noqa: F401
 from .smb_env import SmbGymEnv, SmbVecEnv  # noqa: F401
 from .smb_ready import SmbReadyVecEnv  # noqa: F401
 from .smb_rllib import SmbVectorEnv, make_vector_env  # noqa: F401
-from .loderunner import LodeRunnerEvaluator, loderunner_spec  # noqa: F401
+from .loderunner import LODERUNNER_BC_NAMES, LodeRunnerEvaluator, loderunner_spec  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

@@ -53,6 +53,8 @@
 #include "smb/pcgrl_smb_measures.h"  // level measures and pairwise Hamming diversity of smb maps
 #include "../../include/pcgrl_amd_loderunner.h"
 #include "loderunner/pcgrl_loderunner.h"  // Lode Runner levels: statistics, win score and gold searches
+#include "../../include/pcgrl_amd_loderunner_measures.h"
+#include "loderunner/pcgrl_loderunner_measures.h"  // level measures and pairwise Hamming diversity of Lode Runner maps
 
 using namespace pcgrl;
 
@@ -2236,6 +2238,83 @@ int pcgrl_loderunner_evaluate(const pcgrl_loderunner_config *cfg, int32_t n, con
     a.trg_hi[k] = cfg->trg_hi[k];
   }
   HIPCHK(launch_loderunner(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ Lode Runner maps: level measures and pairwise Hamming diversity
+// include/pcgrl_amd_loderunner_measures.h; the measure / pack kernel in loderunner/pcgrl_loderunner_measures.h, the pairwise
+// kernels those of measures/pcgrl_measures.h.
+
+static void lr_meas_args(MeasWaveArgs &a, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids) {
+  a = MeasWaveArgs{};
+  a.grids = d_grids;
+  a.h = h;
+  a.w = w;
+  a.n = n;
+  a.NW = (h * w + 63) / 64;
+  a.group = 1;
+}
+
+extern "C" {
+
+int pcgrl_loderunner_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
+                                        int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
+                                        void *stream) {
+  const char *who = "pcgrl_loderunner_measures_for_grids";
+  if (n < 0 || (n > 0 && (!d_grids || !d_counts || !d_match || (d_entropy && !d_entropy_tab))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  const int rc = lr_check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  MeasWaveArgs a;
+  lr_meas_args(a, h, w, n, d_grids);
+  a.counts = d_counts;
+  a.match = d_match;
+  a.forms = d_forms;
+  a.entropy = d_entropy;
+  a.tab = d_entropy_tab;
+  HIPCHK(launch_lr_measures(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+size_t pcgrl_loderunner_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
+  if (n <= 0 || h < 1 || h > LR_MAX_H || w < 1 || w > LR_MAX_W) return 0;
+  // the bit-plane image, then one nearest-map key per map
+  return (size_t)n * (LR_MEAS_PLANES * ((h * w + 63) / 64) + 1) * sizeof(uint64_t);
+}
+
+// pack the n maps into d_scratch, then the all-pairs kernel per group and the finish
+int pcgrl_loderunner_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
+                                         void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
+                                         int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  const char *who = "pcgrl_loderunner_diversity_for_grids";
+  if (n < 0 || (n > 0 && (!d_grids || !d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum)))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (group < 2 || n % group != 0)
+    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
+  const int rc = lr_check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  MeasWaveArgs a;
+  lr_meas_args(a, h, w, n, d_grids);
+  a.pack = (uint64_t *)d_scratch;
+  a.sum = (unsigned long long *)d_sum;
+  a.near_key = (unsigned long long *)(a.pack + (size_t)n * LR_MEAS_PLANES * a.NW);
+  a.group = group;
+  HIPCHK(launch_lr_measures(a, (hipStream_t)stream));
+  DivArgs d;
+  d.pack = a.pack;
+  d.n = n;
+  d.K = group;
+  d.P = LR_MEAS_PLANES;
+  d.NW = a.NW;
+  div_splits(n, group, d.splits, d.tiles_per_split);
+  d.sum = a.sum;
+  d.near_key = a.near_key;
+  d.pairwise = d_pairwise;
+  HIPCHK(launch_diversity(d, (hipStream_t)stream));
+  if (d_scores || d_nearest || d_nearest_idx)
+    HIPCHK(launch_diversity_finish(d, h * w, d_nearest, d_nearest_idx, d_scores, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

@@ -1,8 +1,10 @@
 """Lode Runner levels on the device: the five statistics of LoderunnerProblem.get_stats, the loss ControlWrapper.get_loss
 would derive from them and the per-gold record of the gold searches behind `win` and `path-length`, for a batch of maps in one
-launch (include/pcgrl_amd_loderunner.h, csrc/loderunner/pcgrl_loderunner.h).
+launch (include/pcgrl_amd_loderunner.h, csrc/loderunner/pcgrl_loderunner.h); and the level measures,
+the pairwise Hamming diversity and the behaviour vector the reference's quality-diversity loop places a level by
+(include/pcgrl_amd_loderunner_measures.h, csrc/loderunner/pcgrl_loderunner_measures.h).
 
-This module evaluates maps; stepping Lode Runner environments is not built.  It is not part of the 2-D engine, so PROBLEMS /
+This module evaluates and measures maps; stepping Lode Runner environments is not built.  It is not part of the 2-D engine, so PROBLEMS /
 problem_spec / build_config do not know "loderunner".  file:line references are relative to the reference's
 control_pcgrl/envs/probs/ directory.
 
@@ -12,7 +14,9 @@ size the reference's own answer depends on the host's speed.
 """
 import ctypes as C
 import math
+from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -20,6 +24,9 @@ from .problems import ProblemSpec, target_interval
 
 LODERUNNER_TILES = ["empty", "brick", "ladder", "rope", "solid", "gold", "enemy", "player"]  # loderunner_prob.py:46
 LODERUNNER_STAT_KEYS = ["player", "enemies", "gold", "win", "path-length"]
+LODERUNNER_MEASURE_NAMES = ("emptiness", "entropy", "symmetry", "symmetry-horizontal", "symmetry-vertical", "co-occurance")
+# what behaviour() takes: get_bc (evo/evolve.py:606-635) looks in the statistics first, then among the measures of the map
+LODERUNNER_BC_NAMES = tuple(LODERUNNER_STAT_KEYS) + LODERUNNER_MEASURE_NAMES + ("NONE",)
 MAX_H, MAX_W = 16, 32
 
 
@@ -142,14 +149,127 @@ class LodeRunnerEvaluator:
         return out
 
     def check_errors(self):
-        """Raises if a launch since the last check read a tile id above 7 (it was taken as empty).  Synchronises."""
+        """Raises if a launch of evaluate() since the last check read a tile id above 7 (it was taken as empty).  Synchronises.
+        measures() / diversity() mask ids to 3 bits and set no error."""
         bits = int(self._error.item())
         self._error.zero_()
         if bits & 1:
             raise ValueError("loderunner: a tile id above 7 was seen on the device (read as empty)")
 
+    _entropy_tab = None  # built at the first measures(entropy=True)
+
+    def _entropy_table(self):
+        """tab[c] = (c / n) * ln(c / n) for c = 0 .. n, then get_entropy's max_val (evolve.py:436) with T = 8: built once on
+        the host with numpy's scalar log -- the very operations of get_entropy (evolve.py:441-444) -- and uploaded at first use
+        (SmbMeasures._entropy_table with ln 8)"""
+        if self._entropy_tab is None:
+            n, T = self.map_shape[0] * self.map_shape[1], len(LODERUNNER_TILES)
+            tab = np.zeros(n + 2, dtype=np.float64)
+            for c in range(1, n + 1):
+                p = np.int64(c) / n
+                tab[c] = p * np.log(p)
+            tab[n + 1] = -(1 / T) * np.log(1 / T) * T
+            self._entropy_tab = torch.from_numpy(tab).to(self.device)
+        return self._entropy_tab
+
+    def _grids_arg(self, grids):
+        if self._closed:
+            raise RuntimeError("LodeRunnerEvaluator is closed")
+        g = torch.as_tensor(grids, device=self.device)
+        if g.dtype != torch.uint8:
+            g = g.to(torch.uint8)
+        if g.dim() == 2:
+            g = g.unsqueeze(0)
+        if g.dim() != 3 or tuple(g.shape[1:]) != self.map_shape:
+            raise ValueError(f"grids must have shape [n]{list(self.map_shape)}, got {list(g.shape)}")
+        return g.contiguous()
+
+    def measures(self, grids, entropy=True):
+        """The behaviour characteristics of the maps that the reference computes from the integer map (evo/evolve.py:606-635
+        get_bc -> :423-592), as SmbEvaluator.measures returns them with T = 8: counts int32 [n, 8], match int32 [n, 3]
+        (horizontal, vertical, wrapped co-occurance matches), forms float64 [n, 13], tile_fractions float64 [n, 8] and bc, a
+        dict under get_bc's names -> float64 [n] (also .entropy, .emptiness).  All but entropy equal the reference bit for bit;
+        entropy does on the host whose numpy built the table.  The divisors are the map's own H * W.  grids: uint8 [n][H][W] at
+        any alignment, n >= 0; ids are masked to 3 bits and set no error.  One launch on the current stream, no host sync."""
+        g = self._grids_arg(grids)
+        n, dev, T = g.shape[0], self.device, len(LODERUNNER_TILES)
+        H, W = self.map_shape
+        out = SimpleNamespace(counts=torch.empty((n, T), dtype=torch.int32, device=dev),
+                              match=torch.empty((n, 3), dtype=torch.int32, device=dev),
+                              forms=torch.empty((n, 5 + T), dtype=torch.float64, device=dev),
+                              entropy=torch.empty(n, dtype=torch.float64, device=dev) if entropy else None)
+        ent = out.entropy.data_ptr() if entropy else None
+        tab = self._entropy_table().data_ptr() if entropy else None
+        with torch.cuda.device(dev):
+            _lib.check(self._L.pcgrl_loderunner_measures_for_grids(H, W, n, g.data_ptr(), out.counts.data_ptr(),
+                                                                   out.match.data_ptr(), out.forms.data_ptr(), ent, tab,
+                                                                   self._stream()), "pcgrl_loderunner_measures_for_grids")
+        # the float64 forms come from the kernel (correctly rounded divisions in the reference's order): views of its rows
+        f = out.forms
+        out.tile_fractions = f[:, 5:]  # get_counts (evolve.py:461-464)
+        out.bc = {"emptiness": f[:, 0], "symmetry-horizontal": f[:, 1], "symmetry-vertical": f[:, 2], "symmetry": f[:, 3],
+                  "co-occurance": f[:, 4]}
+        if entropy:
+            out.bc["entropy"] = out.entropy
+        out.emptiness = out.bc["emptiness"]
+        return out
+
+    def diversity(self, grids, group=None, pairwise=False):
+        """Pairwise Hamming distances (cells whose tiles differ) among the maps in consecutive groups of `group` maps (None: one
+        group of all), as SmbEvaluator.diversity returns them: hamming_sum int64 [G], scores float64 [G, 2], nearest /
+        nearest_idx int32 [n] (the lowest index on ties), div_score (rl/evaluate_ctrl.py:42-48) and diversity_bonus
+        (evo/evolve.py:1236-1244) float64 [G], pairwise int32 [G, K, K] or None.  Three launches on the current stream, no host
+        sync."""
+        g = self._grids_arg(grids)
+        n, dev = g.shape[0], self.device
+        H, W = self.map_shape
+        K = n if group is None else int(group)
+        if K < 2 or n % K:
+            raise ValueError(f"diversity: group = {K} must be at least 2 and divide the {n} maps")
+        G = n // K
+        nbytes = int(self._L.pcgrl_loderunner_diversity_scratch_bytes(H, W, n))
+        scratch = torch.empty(max(1, nbytes // 8), dtype=torch.int64, device=dev)
+        out = SimpleNamespace(hamming_sum=torch.empty(G, dtype=torch.int64, device=dev),
+                              scores=torch.empty((G, 2), dtype=torch.float64, device=dev),
+                              nearest=torch.empty(n, dtype=torch.int32, device=dev),
+                              nearest_idx=torch.empty(n, dtype=torch.int32, device=dev),
+                              pairwise=torch.empty((G, K, K), dtype=torch.int32, device=dev) if pairwise else None)
+        pw = out.pairwise.data_ptr() if pairwise else None
+        with torch.cuda.device(dev):
+            _lib.check(self._L.pcgrl_loderunner_diversity_for_grids(H, W, n, g.data_ptr(), K, scratch.data_ptr(),
+                                                                    out.hamming_sum.data_ptr(), out.scores.data_ptr(),
+                                                                    out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw,
+                                                                    self._stream()), "pcgrl_loderunner_diversity_for_grids")
+        out.div_score = out.scores[:, 0]  # div_calc (evaluate_ctrl.py:42-48)
+        out.diversity_bonus = out.scores[:, 1]  # evolve.py:1236-1244: N * N - 1, not N * (N - 1)
+        return out
+
+    def behaviour(self, grids, names):
+        """The behaviour vector of each map: float64 [n, len(names)], column j the reference's get_bc(names[j], ...)
+        (evo/evolve.py:606-635).  A name among spec.stat_keys is that column of evaluate()'s stats (get_bc looks there first); a
+        name of LODERUNNER_MEASURE_NAMES is the measure of that name; "NONE" is 0.  evaluate(gold_cap=0) runs only if a
+        statistic is named, the measures launch only if a measure is named, and the entropy is computed only if named.  No host
+        sync.  The quality-diversity loop's pairs for this problem (configs/evo/batch.yaml) are ("emptiness", "path-length") and
+        ("symmetry", "path-length")."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [k for k in names if k not in LODERUNNER_BC_NAMES]
+        if unknown:
+            raise ValueError(f"unknown behaviour characteristics {unknown}: the known names are {list(LODERUNNER_BC_NAMES)}")
+        g = self._grids_arg(grids)
+        stats = self.evaluate(g, gold_cap=0)["stats"] if any(k in LODERUNNER_STAT_KEYS for k in names) else None
+        meas = (self.measures(g, entropy="entropy" in names).bc
+                if any(k in LODERUNNER_MEASURE_NAMES for k in names) else None)
+        out = torch.zeros((g.shape[0], len(names)), dtype=torch.float64, device=self.device)
+        for j, k in enumerate(names):
+            if k in LODERUNNER_STAT_KEYS:
+                out[:, j] = stats[:, LODERUNNER_STAT_KEYS.index(k)]
+            elif k != "NONE":
+                out[:, j] = meas[k]
+        return out
+
     def close(self):
         self._workspace, self._workspace_bytes, self._closed = None, 0, True
+        self._entropy_tab = None
 
     def __enter__(self):
         return self
