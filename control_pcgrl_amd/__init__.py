@@ -16,7 +16,8 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
                            its own; make_vector_env(cfg, n) picks SmbVectorEnv or PcgrlVectorEnv by problem
   LodeRunnerEvaluator      Lode Runner levels: the five statistics, the loss and the per-gold record of the gold searches of a
                            batch of maps in one launch (loderunner_spec() has the problem's tables); measures(), diversity()
-                           and behaviour(): the behaviour vector under the names of LODERUNNER_BC_NAMES
+                           and behaviour(): the behaviour vector under the names of LODERUNNER_BC_NAMES; routes(): the cells
+                           and moves of both A* paths of every counted gold, the tour behind path-length
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of

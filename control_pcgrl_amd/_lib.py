@@ -17,13 +17,14 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip", "smb/pcgrl_k_smb_ready.hip",
          "smb/pcgrl_k_smb_state.hip", "smb/pcgrl_k_smb_rollout.hip", "smb/pcgrl_k_smb_vector.hip",
          "smb/pcgrl_k_smb_measures.hip", "loderunner/pcgrl_k_loderunner.hip",
-         "loderunner/pcgrl_k_loderunner_measures.hip"]
+         "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
            "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h", "smb/pcgrl_smb_state.h",
            "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
-           "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h"]
+           "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
+           "loderunner/pcgrl_loderunner_routes.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -42,6 +43,7 @@ SMB_VECTOR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_s
 SMB_MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_measures.h")
 LODERUNNER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner.h")
 LODERUNNER_MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner_measures.h")
+LODERUNNER_ROUTES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner_routes.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -295,6 +297,12 @@ LODERUNNER_MEASURES_SYMBOLS = {
                                              + [C.c_void_p] * 7),
 }
 
+# include/pcgrl_amd_loderunner_routes.h: the routes behind a Lode Runner level's path-length (the evaluation and the cell lists)
+LODERUNNER_ROUTES_SYMBOLS = {
+    "pcgrl_loderunner_routes": (C.c_int, [C.POINTER(PcgrlLoderunnerConfig), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int32, C.c_int32] + [C.c_void_p] * 12),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -306,7 +314,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                                                        SMB_ENV_HEADER, SMB_READY_HEADER, SMB_STATE_HEADER,
                                                        SMB_ROLLOUT_HEADER, SMB_CTRL_HEADER, SMB_VECTOR_HEADER,
                                                        SMB_MEASURES_HEADER, LODERUNNER_HEADER,
-                                                       LODERUNNER_MEASURES_HEADER]
+                                                       LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -321,7 +329,8 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(SMB_READY_HEADER), os.path.getmtime(SMB_STATE_HEADER),
                    os.path.getmtime(SMB_ROLLOUT_HEADER), os.path.getmtime(SMB_CTRL_HEADER),
                    os.path.getmtime(SMB_VECTOR_HEADER), os.path.getmtime(SMB_MEASURES_HEADER),
-                   os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER))
+                   os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
+                   os.path.getmtime(LODERUNNER_ROUTES_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -372,7 +381,8 @@ def lib():
                                   + list(SMB_READY_SYMBOLS.items()) + list(SMB_STATE_SYMBOLS.items())
                                   + list(SMB_ROLLOUT_SYMBOLS.items()) + list(SMB_CTRL_SYMBOLS.items())
                                   + list(SMB_VECTOR_SYMBOLS.items()) + list(SMB_MEASURES_SYMBOLS.items())
-                                  + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())):
+                                  + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())
+                                  + list(LODERUNNER_ROUTES_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

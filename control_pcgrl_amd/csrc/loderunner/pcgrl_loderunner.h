@@ -27,6 +27,9 @@
 //             cells is the path.  Each lane marks its path's parents in a 512-bit LDS row.
 //   golds     sequential over the round's golds in row-major order, all lanes on the cells: the skip rule, the first search's
 //             node count into path-length, and every unfound gold on a marked cell of either path becomes found.
+//   hooks     lr_evaluate_level takes a hook object (LrNoHook: nothing) that is told of every search, of every pair that counts
+//             and of the end of every round: how loderunner_routes_kernel (pcgrl_loderunner_routes.h) reads the routes out of
+//             the parent chains without a second copy of the search or of the accumulation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -163,9 +166,10 @@ __host__ __device__ constexpr uint32_t lr_order(uint32_t a, uint32_t b, uint32_t
 
 // AStar.run (engine.py:244-269) from cell `src` to cell `goal`, by one lane on its own workspace words (word i at p[i * 64]).
 // Returns the nodes on the path found (steps + 1), 0 when the open list empties; marks the path's parent cells in `marks`
-// (bit p of the lane's row: word p / 32 at marks[(p / 32) * 64]).
+// (bit p of the lane's row: word p / 32 at marks[(p / 32) * 64]).  The goal is never closed, so its parent leaves in
+// `goal_parent` (-1 when the root is the goal); the parents before it stay in `cells` until the lane's next search.
 __device__ inline int lr_search(const LrLds &L, int H, int W, int src, int goal, uint32_t *nodes, uint32_t *buckets, uint32_t *cells,
-                                uint32_t *marks) {
+                                uint32_t *marks, int &goal_parent) {
   const int n_cells = H * W, n_scores = lr_scores(H, W), max_nodes = lr_nodes(n_cells);
   const int gr = goal / W, gc = goal % W;
   for (int i = 0; i < n_cells; i++) cells[i * 64] = 0;
@@ -184,6 +188,7 @@ __device__ inline int lr_search(const LrLds &L, int H, int W, int src, int goal,
     const int cell = nd & 511u, parent = (nd >> 9) & 511u;
     if (cells[cell * 64] & LR_CLOSED) continue;
     if (cell == goal) {
+      goal_parent = head != 0 ? parent : -1;
       if (head != 0) {  // the root as the goal has no parents
         int p = parent;
         for (int guard = 0; guard < n_cells; guard++) {
@@ -222,11 +227,23 @@ __device__ inline int lr_search(const LrLds &L, int H, int W, int src, int goal,
   return 0;
 }
 
+// The hook of lr_evaluate_level that does nothing.  A hook's calls: round_begin by every lane before a round's searches;
+// searched by the lane that ran a search (its goal, the goal's parent, the nodes on the path, 0 = none); counted by every lane,
+// in gold order, for gold j (pair q of its round) whose pair of searches counts, with the nodes of its two paths; round_end
+// by every lane after the round's accumulation, while the lane's parent chain in `cells` still stands.
+struct LrNoHook {
+  __device__ __forceinline__ void round_begin() {}
+  __device__ __forceinline__ void searched(int, int, int) {}
+  __device__ __forceinline__ void counted(int, int, int, int) {}
+  __device__ __forceinline__ void round_end(const uint32_t *) {}
+};
+
 // One level, by one 64-lane wave: the statistics and the gold record of the map in L.map ([H][W], ids 0..7; the landing cell
 // is overwritten).  slot: this block's workspace.  L.state / L.dist / L.golds hold the per-gold record afterwards, r.gold
 // entries.  Every lane returns with the same LrResult.  For a block of exactly one 64-lane wave: the lane id is wave-local, the
 // barriers are block-wide and the LDS rows are indexed by lane, so a kernel with more waves per block must not call it as it is.
-__device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot, LrResult &r) {
+template <class Hook>
+__device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot, LrResult &r, Hook &hook) {
   const int lane = threadIdx.x & 63, n_cells = H * W;
   // counts, the player's cell, the gold list in row-major order
   int players = 0, enemies = 0, golds = 0, pcell = -1;
@@ -277,12 +294,15 @@ __device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot,
     const int j = base + (lane >> 1);
     for (int k = 0; k < (n_cells + 31) / 32; k++) L.marks[k][lane] = 0;
     int len = 0;
+    hook.round_begin();
     if (j < golds && L.state[L.golds[j]] == 0) {
       // source and goal are picked per lane and the search is called once, so the outward and the return searches of the round
       // run in the same instructions, side by side
       const int g = L.golds[j];
       const int src = (lane & 1) ? g : start, goal = (lane & 1) ? start : g;
-      len = lr_search(L, H, W, src, goal, nodes, buckets, cells, &L.marks[0][lane]);
+      int goal_parent = -1;
+      len = lr_search(L, H, W, src, goal, nodes, buckets, cells, &L.marks[0][lane], goal_parent);
+      hook.searched(goal, goal_parent, len);
     }
     L.len[lane] = (uint16_t)len;
     __syncthreads();
@@ -293,6 +313,7 @@ __device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot,
       const bool counts = L.state[g] == 0 && L.len[2 * q] != 0 && L.len[2 * q + 1] != 0;
       __syncthreads();
       if (counts) {
+        hook.counted(q, base + q, L.len[2 * q], L.len[2 * q + 1]);
         total += L.len[2 * q];
         for (int i = lane; i < n_cells; i += 64) {
           const uint32_t bit = (L.marks[i >> 5][2 * q] | L.marks[i >> 5][2 * q + 1]) >> (i & 31);
@@ -305,6 +326,7 @@ __device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot,
       }
       __syncthreads();
     }
+    hook.round_end(cells);
   }
   int found = 0;
   for (int base = 0; base < golds; base += 64) {
@@ -317,7 +339,12 @@ __device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot,
   r.win = 1.0 / (double)(1 + (golds - collected));
 }
 
-#ifndef PCGRL_LR_DEVICE_ONLY  // (a later env kernel takes the device functions above without a second loderunner_kernel)
+__device__ inline void lr_evaluate_level(LrLds &L, int H, int W, uint32_t *slot, LrResult &r) {
+  LrNoHook none;
+  lr_evaluate_level(L, H, W, slot, r, none);
+}
+
+#ifndef PCGRL_LR_DEVICE_ONLY  // (loderunner_routes_kernel takes the device functions above without a second loderunner_kernel)
 __global__ __launch_bounds__(64) void loderunner_kernel(const LrArgs a) {
   __shared__ LrLds L;
   const int lane = threadIdx.x;

@@ -53,6 +53,8 @@
 #include "smb/pcgrl_smb_measures.h"  // level measures and pairwise Hamming diversity of smb maps
 #include "../../include/pcgrl_amd_loderunner.h"
 #include "loderunner/pcgrl_loderunner.h"  // Lode Runner levels: statistics, win score and gold searches
+#include "../../include/pcgrl_amd_loderunner_routes.h"
+#include "loderunner/pcgrl_loderunner_routes.h"  // the routes behind path-length
 #include "../../include/pcgrl_amd_loderunner_measures.h"
 #include "loderunner/pcgrl_loderunner_measures.h"  // level measures and pairwise Hamming diversity of Lode Runner maps
 
@@ -2205,10 +2207,10 @@ int64_t pcgrl_loderunner_workspace_bytes(int32_t n, int32_t h, int32_t w) {
   return (int64_t)lr_blocks(n, h, w) * lr_ws_stride(h, w);
 }
 
-int pcgrl_loderunner_evaluate(const pcgrl_loderunner_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
-                              int64_t workspace_bytes, int32_t gold_cap, double *d_stats, double *d_loss, int32_t *d_play,
-                              int8_t *d_gold_state, int16_t *d_gold_dist, uint32_t *d_error, void *stream) {
-  const char *who = "pcgrl_loderunner_evaluate";
+// the argument checks and the kernel arguments that pcgrl_loderunner_evaluate and pcgrl_loderunner_routes share
+static int lr_fill_args(const char *who, LrArgs &a, const pcgrl_loderunner_config *cfg, int32_t n, const uint8_t *d_grids,
+                        void *d_workspace, int64_t workspace_bytes, int32_t gold_cap, double *d_stats, double *d_loss,
+                        int32_t *d_play, int8_t *d_gold_state, int16_t *d_gold_dist, uint32_t *d_error) {
   if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
   if (gold_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": gold_cap must not be negative");
   const int rc = lr_check_shape(who, cfg->h, cfg->w);
@@ -2217,7 +2219,7 @@ int pcgrl_loderunner_evaluate(const pcgrl_loderunner_config *cfg, int32_t n, con
   if (!d_workspace || ((uintptr_t)d_workspace & 3u) || workspace_bytes < (int64_t)lr_blocks(n, cfg->h, cfg->w) * stride)
     return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 4-byte aligned or smaller than "
                                                  "pcgrl_loderunner_workspace_bytes");
-  LrArgs a = {};
+  a = LrArgs{};
   a.h = cfg->h;
   a.w = cfg->w;
   a.n = n;
@@ -2237,7 +2239,40 @@ int pcgrl_loderunner_evaluate(const pcgrl_loderunner_config *cfg, int32_t n, con
     a.trg_lo[k] = cfg->trg_lo[k];
     a.trg_hi[k] = cfg->trg_hi[k];
   }
+  return PCGRL_OK;
+}
+
+int pcgrl_loderunner_evaluate(const pcgrl_loderunner_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
+                              int64_t workspace_bytes, int32_t gold_cap, double *d_stats, double *d_loss, int32_t *d_play,
+                              int8_t *d_gold_state, int16_t *d_gold_dist, uint32_t *d_error, void *stream) {
+  LrArgs a;
+  const int rc = lr_fill_args("pcgrl_loderunner_evaluate", a, cfg, n, d_grids, d_workspace, workspace_bytes, gold_cap, d_stats,
+                              d_loss, d_play, d_gold_state, d_gold_dist, d_error);
+  if (rc != PCGRL_OK) return rc;
   HIPCHK(launch_loderunner(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+// include/pcgrl_amd_loderunner_routes.h; kernel in loderunner/pcgrl_loderunner_routes.h
+int pcgrl_loderunner_routes(const pcgrl_loderunner_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
+                            int64_t workspace_bytes, int32_t gold_cap, int32_t route_cap, double *d_stats, double *d_loss,
+                            int32_t *d_play, int8_t *d_gold_state, int16_t *d_gold_dist, int32_t *d_gold_off,
+                            int16_t *d_gold_back, int16_t *d_coords, int8_t *d_moves, int32_t *d_tour_len, uint32_t *d_error,
+                            void *stream) {
+  const char *who = "pcgrl_loderunner_routes";
+  LrRouteArgs a = {};
+  const int rc = lr_fill_args(who, a.lr, cfg, n, d_grids, d_workspace, workspace_bytes, gold_cap, d_stats, d_loss, d_play,
+                              d_gold_state, d_gold_dist, d_error);
+  if (rc != PCGRL_OK) return rc;
+  if (route_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": route_cap must not be negative");
+  if (route_cap > 0 && !d_coords) return fail(PCGRL_EINVAL, std::string(who) + ": route_cap > 0 needs d_coords");
+  a.route_cap = route_cap;
+  a.coords = d_coords;
+  a.moves = d_moves;
+  a.tour_len = d_tour_len;
+  a.gold_off = d_gold_off;
+  a.gold_back = d_gold_back;
+  HIPCHK(launch_loderunner_routes(a, (hipStream_t)stream));
   return PCGRL_OK;
 }
 

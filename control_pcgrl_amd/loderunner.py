@@ -2,9 +2,11 @@
 would derive from them and the per-gold record of the gold searches behind `win` and `path-length`, for a batch of maps in one
 launch (include/pcgrl_amd_loderunner.h, csrc/loderunner/pcgrl_loderunner.h); and the level measures,
 the pairwise Hamming diversity and the behaviour vector the reference's quality-diversity loop places a level by
-(include/pcgrl_amd_loderunner_measures.h, csrc/loderunner/pcgrl_loderunner_measures.h).
+(include/pcgrl_amd_loderunner_measures.h, csrc/loderunner/pcgrl_loderunner_measures.h); and the routes
+behind `path-length`, the cells of both A* paths of every gold collected by its own searches
+(include/pcgrl_amd_loderunner_routes.h, csrc/loderunner/pcgrl_loderunner_routes.h).
 
-This module evaluates and measures maps; stepping Lode Runner environments is not built.  It is not part of the 2-D engine, so PROBLEMS /
+This module evaluates and measures maps and lists their routes; stepping Lode Runner environments is not built.  It is not part of the 2-D engine, so PROBLEMS /
 problem_spec / build_config do not know "loderunner".  file:line references are relative to the reference's
 control_pcgrl/envs/probs/ directory.
 
@@ -93,6 +95,15 @@ class LodeRunnerEvaluator:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _grow_workspace(self, n):
+        """the workspace a launch over min(n, max_levels) levels needs (inside torch.cuda.device(self.device))"""
+        need = self._L.pcgrl_loderunner_workspace_bytes(min(n, self.max_levels), self.map_shape[0], self.map_shape[1])
+        if need > self._workspace_bytes:
+            if self._workspace is not None:  # launches already enqueued on this stream keep it until they are done
+                self._workspace.record_stream(torch.cuda.current_stream(self.device))
+            self._workspace = torch.empty(need // 4, dtype=torch.int32, device=self.device)
+            self._workspace_bytes = need
+
     def evaluate(self, grids, gold_cap=32):
         """grids: uint8 [n][H][W] (a device tensor, or anything torch.as_tensor takes).  Returns device tensors: stats float64
         [n][5] (spec.stat_keys order; win and path_length are views of its columns), loss float64 [n], play int32 [n][4]
@@ -130,12 +141,7 @@ class LodeRunnerEvaluator:
 
         with torch.cuda.device(dev):
             stream = self._stream()
-            need = self._L.pcgrl_loderunner_workspace_bytes(min(n, self.max_levels), self.map_shape[0], self.map_shape[1])
-            if need > self._workspace_bytes:
-                if self._workspace is not None:  # launches already enqueued on this stream keep it until they are done
-                    self._workspace.record_stream(torch.cuda.current_stream(dev))
-                self._workspace = torch.empty(need // 4, dtype=torch.int32, device=dev)
-                self._workspace_bytes = need
+            self._grow_workspace(n)
             for lo in range(0, n, self.max_levels):
                 m = min(self.max_levels, n - lo)
                 _lib.check(self._L.pcgrl_loderunner_evaluate(
@@ -148,8 +154,92 @@ class LodeRunnerEvaluator:
         out["path_length"] = out["stats"][:, 4]
         return out
 
+    def routes(self, grids, gold_cap=32, route_cap=None, moves=False):
+        """evaluate() and the routes behind path-length, in one launch per max_levels levels (no second search: the kernel of
+        evaluate() with the parent chains read out).  Returns evaluate()'s dict and, as device tensors,
+          tour_len   int32 [n]: the cells of the level's tour -- for each gold in state 1, in gold order, its outward route
+                     (landing cell ... gold, gold_dist cells: reversed(to_goal.get_path()[0]) of the reference's
+                     find_all_golds) then its return route (gold ... landing cell, gold_back cells)
+          coords     int16 [n][route_cap][2]: the tour as (row, column), (-1, -1) past its end
+          moves      int8 [n][route_cap], if asked: entry k the move from coords[k] to coords[k + 1] (0..5 = left right up down
+                     d-left d-right, the reference's Node.action); -1 at the last cell of each route and past the end
+          gold_off   int32 [n][gold_cap]: where the gold's outward route starts in the tour (its return route at
+                     off + gold_dist); -1 unless the state is 1
+          gold_back  int16 [n][gold_cap]: the cells of the return route; 0 unless the state is 1
+        (gold_off / gold_back with gold_cap > 0).  route_cap=None is 8 * H * W; route_cap=0 stores no cells, and since tour_len
+        and gold_off stay complete whatever the caps cut, it sizes a second call.  split_routes() cuts a level's tour up."""
+        g = self._grids_arg(grids)
+        n = g.shape[0]
+        if n < 1:
+            raise ValueError("no levels to evaluate")
+        gold_cap = int(gold_cap)
+        if gold_cap < 0:
+            raise ValueError("gold_cap must not be negative")
+        route_cap = 8 * self.map_shape[0] * self.map_shape[1] if route_cap is None else int(route_cap)
+        if route_cap < 0:
+            raise ValueError("route_cap must not be negative")
+        dev = self.device
+        out = {"stats": torch.empty((n, 5), dtype=torch.float64, device=dev),
+               "loss": torch.empty(n, dtype=torch.float64, device=dev),
+               "play": torch.empty((n, 4), dtype=torch.int32, device=dev),
+               "tour_len": torch.empty(n, dtype=torch.int32, device=dev),
+               "coords": torch.empty((n, route_cap, 2), dtype=torch.int16, device=dev)}
+        if moves:
+            out["moves"] = torch.empty((n, route_cap), dtype=torch.int8, device=dev)
+        if gold_cap > 0:
+            out["gold_state"] = torch.empty((n, gold_cap), dtype=torch.int8, device=dev)
+            out["gold_dist"] = torch.empty((n, gold_cap), dtype=torch.int16, device=dev)
+            out["gold_off"] = torch.empty((n, gold_cap), dtype=torch.int32, device=dev)
+            out["gold_back"] = torch.empty((n, gold_cap), dtype=torch.int16, device=dev)
+        err = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def ptr(name, lo):
+            return out[name][lo:].data_ptr() if name in out and out[name].numel() else None
+
+        with torch.cuda.device(dev):
+            stream = self._stream()
+            self._grow_workspace(n)
+            for lo in range(0, n, self.max_levels):
+                m = min(self.max_levels, n - lo)
+                _lib.check(self._L.pcgrl_loderunner_routes(
+                    C.byref(self._cfg), m, g[lo:].data_ptr(), self._workspace.data_ptr(), self._workspace_bytes, gold_cap,
+                    route_cap, ptr("stats", lo), ptr("loss", lo), ptr("play", lo), ptr("gold_state", lo), ptr("gold_dist", lo),
+                    ptr("gold_off", lo), ptr("gold_back", lo), ptr("coords", lo), ptr("moves", lo), ptr("tour_len", lo),
+                    err[lo:].data_ptr(), stream), "pcgrl_loderunner_routes")
+        self._error |= err.max()
+        out["error"] = err
+        out["win"] = out["stats"][:, 3]
+        out["path_length"] = out["stats"][:, 4]
+        return out
+
+    @staticmethod
+    def split_routes(result, i):
+        """Level i of a routes() result cut up on the host: a list of (gold_cell, outward, back), one entry per gold in state
+        1 in gold order, each route a list of (row, column) -- outward from the landing cell to gold_cell, back from gold_cell
+        to the landing cell.  Needs gold_off (gold_cap > 0); raises if gold_cap or route_cap cut a route of the level.
+        Synchronises (it copies the level's rows to the host)."""
+        if "gold_off" not in result:
+            raise ValueError("split_routes needs a routes() result with gold_cap > 0")
+        state = np.asarray(torch.as_tensor(result["gold_state"][i]).cpu())
+        dist = np.asarray(torch.as_tensor(result["gold_dist"][i]).cpu())
+        off = np.asarray(torch.as_tensor(result["gold_off"][i]).cpu())
+        back = np.asarray(torch.as_tensor(result["gold_back"][i]).cpu())
+        coords = np.asarray(torch.as_tensor(result["coords"][i]).cpu())
+        tour = int(torch.as_tensor(result["tour_len"][i]).item())
+        if tour > len(coords):
+            raise ValueError(f"level {i}: the tour has {tour} cells, route_cap kept {len(coords)}")
+        out, seen = [], 0
+        for j in np.flatnonzero(state == 1):
+            o, d, b = int(off[j]), int(dist[j]), int(back[j])
+            outward = [(int(r), int(c)) for r, c in coords[o:o + d]]
+            out.append((outward[-1], outward, [(int(r), int(c)) for r, c in coords[o + d:o + d + b]]))
+            seen += d + b
+        if seen != tour:
+            raise ValueError(f"level {i}: gold_cap cut the per-gold record ({seen} of {tour} cells are accounted for)")
+        return out
+
     def check_errors(self):
-        """Raises if a launch of evaluate() since the last check read a tile id above 7 (it was taken as empty).  Synchronises.
+        """Raises if a launch of evaluate() or routes() since the last check read a tile id above 7 (it was taken as empty).  Synchronises.
         measures() / diversity() mask ids to 3 bits and set no error."""
         bits = int(self._error.item())
         self._error.zero_()
