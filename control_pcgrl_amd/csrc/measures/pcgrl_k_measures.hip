@@ -5,9 +5,15 @@
 
 namespace pcgrl {
 
-hipError_t launch_measures(const Params &p, const MeasArgs &a, hipStream_t s) {
+hipError_t launch_measures(const Params &p, const MeasWaveArgs &a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(measures_kernel, dim3(a.n), dim3(64), 0, s, p, a);
+  const dim3 grid(a.n), block(64);
+  switch (p.n_tiles) {  // binary; sokoban; zelda
+    case 2: hipLaunchKernelGGL((measures_kernel<2, 1>), grid, block, 0, s, p, a); break;
+    case 5: hipLaunchKernelGGL((measures_kernel<5, 3>), grid, block, 0, s, p, a); break;
+    case 8: hipLaunchKernelGGL((measures_kernel<8, 3>), grid, block, 0, s, p, a); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

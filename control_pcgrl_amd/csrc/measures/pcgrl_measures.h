@@ -19,11 +19,12 @@
 //   per group of K consecutive maps: S = sum of d over all ordered pairs; nearest[i] = min_{k != i} d(i, k) and the lowest
 //   such k; optionally the full K x K matrix
 //
-// measures_kernel: one 64-lane wave per map, any shape up to 64 x 64.  The map's bytes are staged in LDS with 16-byte loads
-// (caller maps; the aligned 16-byte blocks that hold the map's first and last byte are read whole) or expanded from the
-// engine's bit-planes; per 64-cell chunk a lane holds one cell, __ballot((id >> p) & 1) IS word p of the chunk in the
-// bit-plane image the pairwise kernel reads ([map][P][NW] uint64, NW = ceil(n / 64), tail lanes contribute 0), and the
-// counts and matches are popcounts of ballots; the partner cells come from LDS.  4 112 B of LDS.
+// measures_kernel<T, P>: one 64-lane wave per map, any shape up to 64 x 64; (T, P) = (2, 1) binary, (5, 3) sokoban, (8, 3)
+// zelda.  The map's bytes are staged in LDS with 16-byte loads (caller maps: meas_wave_stage of measures/pcgrl_measures_wave.h)
+// or expanded here from the engine's bit-planes; then meas_wave_body<T, P> of that header: per 64-cell chunk a lane holds one
+// cell, __ballot((id >> p) & 1) IS word p of the chunk in the bit-plane image the pairwise kernel reads ([map][P][NW] uint64,
+// NW = ceil(n / 64), tail lanes contribute 0), and the counts and matches are popcounts of ballots; the partner cells come
+// from LDS.  4 112 B of LDS.
 //
 // diversity_kernel: one 64-lane workgroup owns 64 row maps of one group, one per lane, and walks a range of the group's maps
 // ("columns") in tiles of DIV_TC = 16; the columns of a group are cut into `splits` ranges so that a call fills the device
@@ -41,28 +42,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../pcgrl_common.h"
+#include "pcgrl_measures_wave.h"  // MEAS_FORMS, MeasWaveArgs, the per-map wave body
 
 namespace pcgrl {
 
 constexpr int MEAS_MAX_CELLS = 64 * 64;
-constexpr int MEAS_FORMS = 5;  // emptiness, symmetry-horizontal, symmetry-vertical, symmetry, co-occurance; then T fractions
 constexpr int DIV_TC = 16;  // column maps per LDS tile = running distances per lane
 constexpr int DIV_WC = 4;   // words per plane of the row map held in registers at a time
 constexpr int DIV_TARGET_WGS = 2048;  // one-wave workgroups a call aims for: 2 per SIMD of 256 CUs
-
-struct MeasArgs {
-  const uint8_t *grids;  // uint8 [n][H][W] caller maps, or null: the engine's planes (Params::planes)
-  int32_t n, T, P, NW;
-  int32_t *counts;       // [n][T], or null
-  int32_t *match;        // [n][3], or null
-  double *forms;         // [n][MEAS_FORMS + T], or null (needs the counts and matches computed: any of the three outputs)
-  double *entropy;       // [n], or null
-  const double *tab;     // [H * W + 2] (see "entropy" above); read only with entropy
-  uint64_t *pack;        // [n][P][NW] the bit-plane image, or null
-  unsigned long long *sum;  // with pack: [n / group], zeroed here for diversity_kernel's atomic adds
-  unsigned long long *near_key;  // with pack: [n], set to all ones here for diversity_kernel's atomic mins
-  int32_t group;
-};
 
 struct DivArgs {
   const uint64_t *pack;  // [n][P][NW]
@@ -89,7 +76,8 @@ inline int meas_planes(int n_tiles) {
   return p;
 }
 
-hipError_t launch_measures(const Params &p, const MeasArgs &a, hipStream_t s);
+// a.grids null: the engine's own maps (p.planes); a.h, a.w the engine's map shape, T = p.n_tiles one of 2, 5, 8
+hipError_t launch_measures(const Params &p, const MeasWaveArgs &a, hipStream_t s);
 hipError_t launch_diversity(const DivArgs &a, hipStream_t s);
 // nearest / nearest_idx from the keys (each may be null); scores[g] = (div_calc, diversity_bonus) of sum[g] (may be null)
 hipError_t launch_diversity_finish(const DivArgs &a, int32_t n_cells, int32_t *nearest, int32_t *nearest_idx, double *scores,
@@ -102,28 +90,27 @@ hipError_t launch_diversity_finish(const DivArgs &a, int32_t n_cells, int32_t *n
 
 namespace pcgrl {
 
-__global__ __launch_bounds__(64) void measures_kernel(Params p, MeasArgs a) {
+template <int T, int P>
+__global__ __launch_bounds__(64) void measures_kernel(Params p, MeasWaveArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t cells[MEAS_MAX_CELLS + 16];
   const int lane = threadIdx.x, e = blockIdx.x;
-  const int H = p.cfg.dims[0], W = p.cfg.dims[1], n = H * W;
-  const int dr = 64 / W, dc = 64 - dr * W;  // 64 cells further on: dr rows and dc columns
-  int off = 0;
+  const uint8_t *m = cells;
   if (a.grids != nullptr) {
-    const uint8_t *src = a.grids + (size_t)e * n;
-    off = (int)((uintptr_t)src & 15u);
-    const uint4 *s16 = (const uint4 *)(src - off);
-    const int nv = (off + n + 15) >> 4;  // <= 257
-    for (int i = lane; i < nv; i += 64) ((uint4 *)cells)[i] = s16[i];
+    m = meas_wave_stage(a, e, cells);
   } else {
+    const int H = a.h, W = a.w, n = H * W;
+    const int dr = 64 / W, dc = 64 - dr * W;  // 64 cells further on: dr rows and dc columns
     int r = lane / W, c = lane - r * W;
     for (int i = lane; i < n; i += 64) {
       int id = 0;
       if (W > 32) {
         const uint64_t *pl = (const uint64_t *)p.planes + (size_t)e * ROW_WORDS * H;
-        for (int k = 0; k < a.P; k++) id |= (int)((pl[k * H + r] >> c) & 1u) << k;
+#pragma unroll
+        for (int k = 0; k < P; k++) id |= (int)((pl[k * H + r] >> c) & 1u) << k;
       } else {
         const uint32_t *pl = (const uint32_t *)p.planes + (size_t)e * ROW_WORDS * H;
-        for (int k = 0; k < a.P; k++) id |= (int)((pl[k * H + r] >> c) & 1u) << k;
+#pragma unroll
+        for (int k = 0; k < P; k++) id |= (int)((pl[k * H + r] >> c) & 1u) << k;
       }
       cells[i] = (uint8_t)id;
       c += dc;
@@ -133,86 +120,9 @@ __global__ __launch_bounds__(64) void measures_kernel(Params p, MeasArgs a) {
         r++;
       }
     }
+    __syncthreads();
   }
-  __syncthreads();
-  const uint8_t *m = cells + off;
-  const int idmask = (1 << a.P) - 1;
-  const bool want_counts = a.counts != nullptr || a.entropy != nullptr || a.forms != nullptr;
-  const bool want_match = a.match != nullptr || a.forms != nullptr;
-  uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t hor = 0, ver = 0, co = 0;
-  int r = lane / W, c = lane - r * W;
-  for (int ch = 0; ch < a.NW; ch++) {
-    const int i = ch * 64 + lane;
-    const bool ok = i < n;
-    const int rr = ok ? r : 0, cc = ok ? c : 0;
-    const int id = m[ok ? i : 0] & idmask;
-    if (a.pack != nullptr) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        if (k < a.P) {
-          const uint64_t w = __ballot(ok && ((id >> k) & 1));
-          if (lane == 0) a.pack[((size_t)e * a.P + k) * a.NW + ch] = w;
-        }
-      }
-    }
-    if (want_counts) {
-#pragma unroll
-      for (int t = 0; t < 8; t++)
-        if (t < a.T) cnt[t] += (uint32_t)__popcll(__ballot(ok && id == t));
-    }
-    if (want_match) {
-      const int up = rr == 0 ? H - 1 : rr - 1, down = rr == H - 1 ? 0 : rr + 1;
-      const int left = cc == 0 ? W - 1 : cc - 1, right = cc == W - 1 ? 0 : cc + 1;
-      hor += (uint32_t)__popcll(__ballot(ok && rr < H / 2 && (m[(H - 1 - rr) * W + cc] & idmask) == id));
-      ver += (uint32_t)__popcll(__ballot(ok && cc < W / 2 && (m[rr * W + (W - 1 - cc)] & idmask) == id));
-      co += (uint32_t)__popcll(__ballot(ok && (m[up * W + cc] & idmask) == id));
-      co += (uint32_t)__popcll(__ballot(ok && (m[down * W + cc] & idmask) == id));
-      co += (uint32_t)__popcll(__ballot(ok && (m[rr * W + left] & idmask) == id));
-      co += (uint32_t)__popcll(__ballot(ok && (m[rr * W + right] & idmask) == id));
-    }
-    c += dc;
-    r += dr;
-    if (c >= W) {
-      c -= W;
-      r++;
-    }
-  }
-  if (lane != 0) return;
-  if (a.counts != nullptr) {
-#pragma unroll
-    for (int t = 0; t < 8; t++)
-      if (t < a.T) a.counts[(size_t)e * a.T + t] = (int32_t)cnt[t];
-  }
-  if (a.match != nullptr) {
-    a.match[(size_t)e * 3] = (int32_t)hor;
-    a.match[(size_t)e * 3 + 1] = (int32_t)ver;
-    a.match[(size_t)e * 3 + 2] = (int32_t)co;
-  }
-  if (a.forms != nullptr) {
-    double *f = a.forms + (size_t)e * (MEAS_FORMS + a.T);
-    const double cells = (double)n, half = (double)(W * H) / 2.0;  // (38.5 for 7 x 11: evolve.py:507, :540)
-    const double h = (double)hor / half, v = (double)ver / half;
-    f[0] = (double)cnt[0] / cells;
-    f[1] = h;
-    f[2] = v;
-    f[3] = (v + h) / 2.0;
-    f[4] = (double)co / (double)(n * 4);
-#pragma unroll
-    for (int t = 0; t < 8; t++)
-      if (t < a.T) f[MEAS_FORMS + t] = (double)cnt[t] / cells;
-  }
-  if (a.entropy != nullptr) {
-    double ent = 0.0;
-#pragma unroll
-    for (int t = 0; t < 8; t++)
-      if (t < a.T && cnt[t] != 0) ent -= a.tab[cnt[t]];
-    a.entropy[e] = ent / a.tab[n + 1];
-  }
-  if (a.pack != nullptr) {
-    if (e % a.group == 0) a.sum[e / a.group] = 0ull;
-    a.near_key[e] = ~0ull;
-  }
+  meas_wave_body<T, P>(a, e, m);
 }
 
 template <int P>

@@ -1889,110 +1889,163 @@ int pcgrl_solutions_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids,
   return solutions_launch(h, "pcgrl_solutions_for_grids", false, n, d_grids, cap, d_moves, d_len, d_dist_win, stream);
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------- measures and diversity
-// include/pcgrl_amd_measures.h; kernels in measures/pcgrl_measures.h
+// The measure / pack step and the pairwise step are the same for every problem: one host path, composed by the entry points of
+// include/pcgrl_amd_measures.h (below), include/pcgrl_amd_loderunner_measures.h and include/pcgrl_amd_smb_measures.h (further
+// down).  An entry point checks its own preconditions (a null handle, the 3-D refusal, its shape range), calls the pointer
+// check here before any HIP call, and hands the arguments and its measure / pack launch to an enqueue.  Kernels in
+// measures/pcgrl_measures.h and, the per-map wave body, measures/pcgrl_measures_wave.h.
+
+// map e at d_grids + e * stride (null: the 2-D engine's own planes), h x w cells each
+static MeasWaveArgs meas_args(const uint8_t *d_grids, int32_t stride, int32_t h, int32_t w, int32_t n) {
+  MeasWaveArgs a{};
+  a.grids = d_grids;
+  a.stride = stride;
+  a.h = h;
+  a.w = w;
+  a.n = n;
+  a.NW = (h * w + 63) / 64;
+  a.group = 1;
+  return a;
+}
+
+// the pointer checks of a measures call (`caller`: the call takes caller maps, so it needs d_grids)
+static int measures_check(const char *who, bool caller, int32_t n, const uint8_t *d_grids, const int32_t *d_counts,
+                          const int32_t *d_match, const double *d_entropy, const double *d_tab) {
+  if (n < 0 || (n > 0 && (!d_counts || !d_match || (d_entropy && !d_tab) || (caller && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  return PCGRL_OK;
+}
+
+// the pointer checks of a diversity call, then the group
+static int diversity_check(const char *who, bool caller, int32_t n, const uint8_t *d_grids, int32_t group, const void *d_scratch,
+                           const int64_t *d_sum) {
+  if (n < 0 || (n > 0 && (!d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum || (caller && !d_grids))))
+    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (group < 2 || n % group != 0)
+    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
+  return PCGRL_OK;
+}
+
+// `launch(a, stream)` is the problem's measure / pack kernel (launch_smb_measures, launch_lr_measures, or launch_measures
+// bound to an engine's Params)
+template <class Launch>
+static int measures_enqueue(MeasWaveArgs a, Launch launch, int32_t *d_counts, int32_t *d_match, double *d_forms,
+                            double *d_entropy, const double *d_tab, void *stream) {
+  a.counts = d_counts;
+  a.match = d_match;
+  a.forms = d_forms;
+  a.entropy = d_entropy;
+  a.tab = d_tab;
+  HIPCHK(launch(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+// the bit-plane image of n maps of P planes, then one nearest-map key per map
+static size_t diversity_scratch_bytes(int P, int32_t h, int32_t w, int32_t n) {
+  return (size_t)n * (P * ((h * w + 63) / 64) + 1) * sizeof(uint64_t);
+}
+
+// pack the n maps into d_scratch, then the all-pairs kernel per group and the finish
+template <class Launch>
+static int diversity_enqueue(MeasWaveArgs a, int P, Launch launch, int32_t group, void *d_scratch, int64_t *d_sum,
+                             double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  a.pack = (uint64_t *)d_scratch;
+  a.sum = (unsigned long long *)d_sum;
+  a.near_key = (unsigned long long *)(a.pack + (size_t)a.n * P * a.NW);
+  a.group = group;
+  HIPCHK(launch(a, (hipStream_t)stream));
+  DivArgs d;
+  d.pack = a.pack;
+  d.n = a.n;
+  d.K = group;
+  d.P = P;
+  d.NW = a.NW;
+  div_splits(a.n, group, d.splits, d.tiles_per_split);
+  d.sum = a.sum;
+  d.near_key = a.near_key;
+  d.pairwise = d_pairwise;
+  HIPCHK(launch_diversity(d, (hipStream_t)stream));
+  if (d_scores || d_nearest || d_nearest_idx)
+    HIPCHK(launch_diversity_finish(d, a.h * a.w, d_nearest, d_nearest_idx, d_scores, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+// include/pcgrl_amd_measures.h: the 2-D engine's maps (`own`) or caller maps of its problem and shape
 static const char *MEASURES_3D =
     ": 2-D problems only (the reference's get_counts reads an attribute the 3-D maze does not have and get_co looks at two "
     "axes only)";
+
+static int measures_2d_refuse(pcgrl_handle h, const char *who) {
+  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (h->p.cfg.ndim != 2) return fail(PCGRL_EUNSUPPORTED, std::string(who) + MEASURES_3D);
+  return PCGRL_OK;
+}
+
+static MeasWaveArgs meas_args_2d(pcgrl_handle h, bool own, int32_t n, const uint8_t *d_grids) {
+  const int32_t H = h->p.cfg.dims[0], W = h->p.cfg.dims[1];
+  return meas_args(own ? nullptr : d_grids, H * W, H, W, n);
+}
+
+static int measures_2d(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
+                       int32_t *d_match, double *d_forms, double *d_entropy, const double *d_tab, void *stream) {
+  int rc = measures_2d_refuse(h, who);
+  if (rc == PCGRL_OK) rc = measures_check(who, !own, n, d_grids, d_counts, d_match, d_entropy, d_tab);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  ON_DEVICE(h->device);
+  return measures_enqueue(meas_args_2d(h, own, n, d_grids),
+                          [h](const MeasWaveArgs &a, hipStream_t s) { return launch_measures(h->p, a, s); }, d_counts, d_match,
+                          d_forms, d_entropy, d_tab, stream);
+}
+
+static int diversity_2d(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t group,
+                        void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
+                        int32_t *d_pairwise, void *stream) {
+  int rc = measures_2d_refuse(h, who);
+  if (rc == PCGRL_OK) rc = diversity_check(who, !own, n, d_grids, group, d_scratch, d_sum);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  ON_DEVICE(h->device);
+  return diversity_enqueue(meas_args_2d(h, own, n, d_grids), meas_planes(h->p.n_tiles),
+                           [h](const MeasWaveArgs &a, hipStream_t s) { return launch_measures(h->p, a, s); }, group, d_scratch,
+                           d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+}
+
+extern "C" {
 
 int32_t pcgrl_measures_tiles(pcgrl_handle h) {
   if (!h) return -1;
   return h->p.cfg.ndim == 2 ? h->p.n_tiles : 0;
 }
 
-static void meas_args_for(pcgrl_handle h, int32_t n, const uint8_t *d_grids, MeasArgs &a) {
-  a = MeasArgs{};
-  a.grids = d_grids;
-  a.n = n;
-  a.T = h->p.n_tiles;
-  a.P = meas_planes(h->p.n_tiles);
-  a.NW = (h->p.cfg.dims[0] * h->p.cfg.dims[1] + 63) / 64;
-  a.group = 1;
-}
-
-static int measures_launch(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
-                           int32_t *d_match, double *d_forms, double *d_entropy, const double *d_tab, void *stream) {
-  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (h->p.cfg.ndim != 2) return fail(PCGRL_EUNSUPPORTED, std::string(who) + MEASURES_3D);
-  if (n < 0 || (n > 0 && (!d_counts || !d_match || (d_entropy && !d_tab) || (!own && !d_grids))))
-    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (n == 0) return PCGRL_OK;
-  ON_DEVICE(h->device);
-  MeasArgs a;
-  meas_args_for(h, n, own ? nullptr : d_grids, a);
-  a.counts = d_counts;
-  a.match = d_match;
-  a.forms = d_forms;
-  a.entropy = d_entropy;
-  a.tab = d_tab;
-  HIPCHK(launch_measures(h->p, a, (hipStream_t)stream));
-  return PCGRL_OK;
-}
-
 int pcgrl_measures(pcgrl_handle h, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
                    const double *d_entropy_tab, void *stream) {
-  return measures_launch(h, "pcgrl_measures", true, h ? h->p.n_envs : 0, nullptr, d_counts, d_match, d_forms, d_entropy,
-                         d_entropy_tab, stream);
+  return measures_2d(h, "pcgrl_measures", true, h ? h->p.n_envs : 0, nullptr, d_counts, d_match, d_forms, d_entropy,
+                     d_entropy_tab, stream);
 }
 
 int pcgrl_measures_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
                              double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
-  return measures_launch(h, "pcgrl_measures_for_grids", false, n, d_grids, d_counts, d_match, d_forms, d_entropy, d_entropy_tab,
-                         stream);
+  return measures_2d(h, "pcgrl_measures_for_grids", false, n, d_grids, d_counts, d_match, d_forms, d_entropy, d_entropy_tab,
+                     stream);
 }
 
 size_t pcgrl_diversity_scratch_bytes(pcgrl_handle h, int32_t n) {
   if (!h || n <= 0 || h->p.cfg.ndim != 2) return 0;
-  // the bit-plane image, then one nearest-map key per map
-  return (size_t)n * (meas_planes(h->p.n_tiles) * ((h->p.cfg.dims[0] * h->p.cfg.dims[1] + 63) / 64) + 1) * sizeof(uint64_t);
-}
-
-// pack the n maps -- the engine's own or the caller's -- into d_scratch, then the all-pairs kernel per group
-static int diversity_launch(pcgrl_handle h, const char *who, bool own, int32_t n, const uint8_t *d_grids, int32_t group,
-                            void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
-                            int32_t *d_pairwise, void *stream) {
-  if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (h->p.cfg.ndim != 2) return fail(PCGRL_EUNSUPPORTED, std::string(who) + MEASURES_3D);
-  if (n < 0 || (n > 0 && (!d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum || (!own && !d_grids))))
-    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (group < 2 || n % group != 0)
-    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
-  if (n == 0) return PCGRL_OK;
-  ON_DEVICE(h->device);
-  MeasArgs a;
-  meas_args_for(h, n, own ? nullptr : d_grids, a);
-  a.pack = (uint64_t *)d_scratch;
-  a.sum = (unsigned long long *)d_sum;
-  a.near_key = (unsigned long long *)(a.pack + (size_t)n * a.P * a.NW);
-  a.group = group;
-  HIPCHK(launch_measures(h->p, a, (hipStream_t)stream));
-  DivArgs d;
-  d.pack = a.pack;
-  d.n = n;
-  d.K = group;
-  d.P = a.P;
-  d.NW = a.NW;
-  div_splits(n, group, d.splits, d.tiles_per_split);
-  d.sum = a.sum;
-  d.near_key = a.near_key;
-  d.pairwise = d_pairwise;
-  HIPCHK(launch_diversity(d, (hipStream_t)stream));
-  if (d_scores || d_nearest || d_nearest_idx)
-    HIPCHK(launch_diversity_finish(d, h->p.cfg.dims[0] * h->p.cfg.dims[1], d_nearest, d_nearest_idx, d_scores,
-                                   (hipStream_t)stream));
-  return PCGRL_OK;
+  return diversity_scratch_bytes(meas_planes(h->p.n_tiles), h->p.cfg.dims[0], h->p.cfg.dims[1], n);
 }
 
 int pcgrl_diversity(pcgrl_handle h, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
                     int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
-  return diversity_launch(h, "pcgrl_diversity", true, h ? h->p.n_envs : 0, nullptr, group, d_scratch, d_sum, d_scores, d_nearest,
-                          d_nearest_idx, d_pairwise, stream);
+  return diversity_2d(h, "pcgrl_diversity", true, h ? h->p.n_envs : 0, nullptr, group, d_scratch, d_sum, d_scores, d_nearest,
+                      d_nearest_idx, d_pairwise, stream);
 }
 
 int pcgrl_diversity_for_grids(pcgrl_handle h, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch, int64_t *d_sum,
                               double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
-  return diversity_launch(h, "pcgrl_diversity_for_grids", false, n, d_grids, group, d_scratch, d_sum, d_scores, d_nearest,
-                          d_nearest_idx, d_pairwise, stream);
+  return diversity_2d(h, "pcgrl_diversity_for_grids", false, n, d_grids, group, d_scratch, d_sum, d_scores, d_nearest,
+                      d_nearest_idx, d_pairwise, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- multi-agent turtle stepping
@@ -2280,17 +2333,7 @@ int pcgrl_loderunner_routes(const pcgrl_loderunner_config *cfg, int32_t n, const
 
 // ------------------------------------------------------------ Lode Runner maps: level measures and pairwise Hamming diversity
 // include/pcgrl_amd_loderunner_measures.h; the measure / pack kernel in loderunner/pcgrl_loderunner_measures.h, the pairwise
-// kernels those of measures/pcgrl_measures.h.
-
-static void lr_meas_args(MeasWaveArgs &a, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids) {
-  a = MeasWaveArgs{};
-  a.grids = d_grids;
-  a.h = h;
-  a.w = w;
-  a.n = n;
-  a.NW = (h * w + 63) / 64;
-  a.group = 1;
-}
+// kernels those of measures/pcgrl_measures.h; the host path is the one of "measures and diversity" above.
 
 extern "C" {
 
@@ -2298,59 +2341,27 @@ int pcgrl_loderunner_measures_for_grids(int32_t h, int32_t w, int32_t n, const u
                                         int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
                                         void *stream) {
   const char *who = "pcgrl_loderunner_measures_for_grids";
-  if (n < 0 || (n > 0 && (!d_grids || !d_counts || !d_match || (d_entropy && !d_entropy_tab))))
-    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  const int rc = lr_check_shape(who, h, w);
+  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
+  if (rc == PCGRL_OK) rc = lr_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
-  MeasWaveArgs a;
-  lr_meas_args(a, h, w, n, d_grids);
-  a.counts = d_counts;
-  a.match = d_match;
-  a.forms = d_forms;
-  a.entropy = d_entropy;
-  a.tab = d_entropy_tab;
-  HIPCHK(launch_lr_measures(a, (hipStream_t)stream));
-  return PCGRL_OK;
+  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_lr_measures, d_counts, d_match, d_forms, d_entropy,
+                          d_entropy_tab, stream);
 }
 
 size_t pcgrl_loderunner_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
   if (n <= 0 || h < 1 || h > LR_MAX_H || w < 1 || w > LR_MAX_W) return 0;
-  // the bit-plane image, then one nearest-map key per map
-  return (size_t)n * (LR_MEAS_PLANES * ((h * w + 63) / 64) + 1) * sizeof(uint64_t);
+  return diversity_scratch_bytes(LR_MEAS_PLANES, h, w, n);
 }
 
-// pack the n maps into d_scratch, then the all-pairs kernel per group and the finish
 int pcgrl_loderunner_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
                                          void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
                                          int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
   const char *who = "pcgrl_loderunner_diversity_for_grids";
-  if (n < 0 || (n > 0 && (!d_grids || !d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum)))
-    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (group < 2 || n % group != 0)
-    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
-  const int rc = lr_check_shape(who, h, w);
+  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
+  if (rc == PCGRL_OK) rc = lr_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
-  MeasWaveArgs a;
-  lr_meas_args(a, h, w, n, d_grids);
-  a.pack = (uint64_t *)d_scratch;
-  a.sum = (unsigned long long *)d_sum;
-  a.near_key = (unsigned long long *)(a.pack + (size_t)n * LR_MEAS_PLANES * a.NW);
-  a.group = group;
-  HIPCHK(launch_lr_measures(a, (hipStream_t)stream));
-  DivArgs d;
-  d.pack = a.pack;
-  d.n = n;
-  d.K = group;
-  d.P = LR_MEAS_PLANES;
-  d.NW = a.NW;
-  div_splits(n, group, d.splits, d.tiles_per_split);
-  d.sum = a.sum;
-  d.near_key = a.near_key;
-  d.pairwise = d_pairwise;
-  HIPCHK(launch_diversity(d, (hipStream_t)stream));
-  if (d_scores || d_nearest || d_nearest_idx)
-    HIPCHK(launch_diversity_finish(d, h * w, d_nearest, d_nearest_idx, d_scores, (hipStream_t)stream));
-  return PCGRL_OK;
+  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), LR_MEAS_PLANES, launch_lr_measures, group, d_scratch, d_sum,
+                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"
@@ -2429,6 +2440,8 @@ int pcgrl_smb_env_create(const pcgrl_smb_env_config *cfg, int32_t device, void *
   a.max_changes = cfg->max_changes;
   a.power = cfg->solver_power;
   a.n = cfg->n_envs;
+  // H * W rounded up to 16 on hipMalloc's aligned base: what the generic staging of measures/pcgrl_measures_wave.h needs to
+  // read an env's rows with no load outside them
   a.map_stride = (cfg->h * cfg->w + 15) / 16 * 16;
   a.ws = (uint8_t *)d_workspace;
   a.ws_stride = stride;
@@ -3088,7 +3101,7 @@ int pcgrl_smb_env_observe_f32(pcgrl_smb_env_handle h, float *out, void *stream) 
 
 // ------------------------------------------------------- Super Mario Bros maps: level measures and pairwise Hamming diversity
 // include/pcgrl_amd_smb_measures.h; the measure / pack kernel in smb/pcgrl_smb_measures.h, the pairwise kernels those of
-// measures/pcgrl_measures.h.
+// measures/pcgrl_measures.h; the host path is the one of "measures and diversity" above.
 
 static int smb_meas_check_shape(const char *who, int32_t h, int32_t w) {
   if (h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W)
@@ -3097,122 +3110,61 @@ static int smb_meas_check_shape(const char *who, int32_t h, int32_t w) {
   return PCGRL_OK;
 }
 
-static void smb_meas_args(SmbMeasArgs &a, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, const pcgrl_smb_env *env) {
-  a = SmbMeasArgs{};
-  a.grids = d_grids;
-  if (env) {
-    a.maps = env->a.maps;
-    a.map_stride = env->a.map_stride;
-  }
-  a.h = h;
-  a.w = w;
-  a.n = n;
-  a.NW = (h * w + 63) / 64;
-  a.group = 1;
-}
-
-// the checks of a measures call, before any HIP call (`env`: the handle's maps, no d_grids)
-static int smb_measures_check(const char *who, bool env, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids,
-                              const int32_t *d_counts, const int32_t *d_match, const double *d_entropy, const double *d_tab) {
-  if (n < 0 || (n > 0 && (!d_counts || !d_match || (d_entropy && !d_tab) || (!env && !d_grids))))
-    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  return smb_meas_check_shape(who, h, w);
-}
-
-static int smb_measures_enqueue(SmbMeasArgs &a, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
-                                const double *d_tab, void *stream) {
-  a.counts = d_counts;
-  a.match = d_match;
-  a.forms = d_forms;
-  a.entropy = d_entropy;
-  a.tab = d_tab;
-  HIPCHK(launch_smb_measures(a, (hipStream_t)stream));
-  return PCGRL_OK;
-}
-
-static int smb_diversity_check(const char *who, bool env, int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
-                               const void *d_scratch, const int64_t *d_sum) {
-  if (n < 0 || (n > 0 && (!d_scratch || ((uintptr_t)d_scratch & 7u) || !d_sum || (!env && !d_grids))))
-    return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (group < 2 || n % group != 0)
-    return fail(PCGRL_EINVAL, std::string(who) + ": group must be at least 2 and divide the number of maps");
-  return smb_meas_check_shape(who, h, w);
-}
-
-// pack the n maps into d_scratch, then the all-pairs kernel per group and the finish
-static int smb_diversity_enqueue(SmbMeasArgs &a, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores,
-                                 int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
-  a.pack = (uint64_t *)d_scratch;
-  a.sum = (unsigned long long *)d_sum;
-  a.near_key = (unsigned long long *)(a.pack + (size_t)a.n * SMB_MEAS_PLANES * a.NW);
-  a.group = group;
-  HIPCHK(launch_smb_measures(a, (hipStream_t)stream));
-  DivArgs d;
-  d.pack = a.pack;
-  d.n = a.n;
-  d.K = group;
-  d.P = SMB_MEAS_PLANES;
-  d.NW = a.NW;
-  div_splits(a.n, group, d.splits, d.tiles_per_split);
-  d.sum = a.sum;
-  d.near_key = a.near_key;
-  d.pairwise = d_pairwise;
-  HIPCHK(launch_diversity(d, (hipStream_t)stream));
-  if (d_scores || d_nearest || d_nearest_idx)
-    HIPCHK(launch_diversity_finish(d, a.h * a.w, d_nearest, d_nearest_idx, d_scores, (hipStream_t)stream));
-  return PCGRL_OK;
+// an env handle's committed maps: rows of map_stride bytes on a 16-byte aligned base (pcgrl_smb_env_create)
+static MeasWaveArgs smb_env_meas_args(const pcgrl_smb_env *e) {
+  return meas_args(e->a.maps, e->a.map_stride, e->a.h, e->a.w, e->a.n);
 }
 
 extern "C" {
 
 int pcgrl_smb_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
                                  double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
-  const int rc = smb_measures_check("pcgrl_smb_measures_for_grids", false, h, w, n, d_grids, d_counts, d_match, d_entropy,
-                                    d_entropy_tab);
+  const char *who = "pcgrl_smb_measures_for_grids";
+  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
+  if (rc == PCGRL_OK) rc = smb_meas_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
-  SmbMeasArgs a;
-  smb_meas_args(a, h, w, n, d_grids, nullptr);
-  return smb_measures_enqueue(a, d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
+  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_smb_measures, d_counts, d_match, d_forms, d_entropy,
+                          d_entropy_tab, stream);
 }
 
 size_t pcgrl_smb_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
   if (n <= 0 || h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W) return 0;
-  // the bit-plane image, then one nearest-map key per map
-  return (size_t)n * (SMB_MEAS_PLANES * ((h * w + 63) / 64) + 1) * sizeof(uint64_t);
+  return diversity_scratch_bytes(SMB_MEAS_PLANES, h, w, n);
 }
 
 int pcgrl_smb_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch,
                                   int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
                                   int32_t *d_pairwise, void *stream) {
-  const int rc = smb_diversity_check("pcgrl_smb_diversity_for_grids", false, h, w, n, d_grids, group, d_scratch, d_sum);
+  const char *who = "pcgrl_smb_diversity_for_grids";
+  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
+  if (rc == PCGRL_OK) rc = smb_meas_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
-  SmbMeasArgs a;
-  smb_meas_args(a, h, w, n, d_grids, nullptr);
-  return smb_diversity_enqueue(a, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), SMB_MEAS_PLANES, launch_smb_measures, group, d_scratch, d_sum,
+                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 int pcgrl_smb_env_measures(pcgrl_smb_env_handle h, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
                            const double *d_entropy_tab, void *stream) {
   const char *who = "pcgrl_smb_env_measures";
   if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
-  const int rc = smb_measures_check(who, true, h->a.h, h->a.w, h->a.n, nullptr, d_counts, d_match, d_entropy, d_entropy_tab);
+  int rc = measures_check(who, false, h->a.n, nullptr, d_counts, d_match, d_entropy, d_entropy_tab);
+  if (rc == PCGRL_OK) rc = smb_meas_check_shape(who, h->a.h, h->a.w);
   if (rc != PCGRL_OK) return rc;
   ON_DEVICE(h->device);
-  SmbMeasArgs a;
-  smb_meas_args(a, h->a.h, h->a.w, h->a.n, nullptr, h);
-  return smb_measures_enqueue(a, d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
+  return measures_enqueue(smb_env_meas_args(h), launch_smb_measures, d_counts, d_match, d_forms, d_entropy, d_entropy_tab,
+                          stream);
 }
 
 int pcgrl_smb_env_diversity(pcgrl_smb_env_handle h, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores,
                             int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
   const char *who = "pcgrl_smb_env_diversity";
   if (!h) return fail(PCGRL_EINVAL, std::string(who) + ": null handle");
-  const int rc = smb_diversity_check(who, true, h->a.h, h->a.w, h->a.n, nullptr, group, d_scratch, d_sum);
+  int rc = diversity_check(who, false, h->a.n, nullptr, group, d_scratch, d_sum);
+  if (rc == PCGRL_OK) rc = smb_meas_check_shape(who, h->a.h, h->a.w);
   if (rc != PCGRL_OK) return rc;
   ON_DEVICE(h->device);
-  SmbMeasArgs a;
-  smb_meas_args(a, h->a.h, h->a.w, h->a.n, nullptr, h);
-  return smb_diversity_enqueue(a, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_enqueue(smb_env_meas_args(h), SMB_MEAS_PLANES, launch_smb_measures, group, d_scratch, d_sum, d_scores,
+                           d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 
 namespace pcgrl {
 
-hipError_t launch_smb_measures(const SmbMeasArgs &a, hipStream_t s) {
+hipError_t launch_smb_measures(const MeasWaveArgs &a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(smb_measures_kernel, dim3(a.n), dim3(64), 0, s, a);
   return hipGetLastError();

@@ -16,12 +16,12 @@ size the reference's own answer depends on the host's speed.
 """
 import ctypes as C
 import math
-from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _lib
+from .measures import MeasuresMixin
 from .problems import ProblemSpec, target_interval
 
 LODERUNNER_TILES = ["empty", "brick", "ladder", "rope", "solid", "gold", "enemy", "player"]  # loderunner_prob.py:46
@@ -64,7 +64,7 @@ def loderunner_config(map_shape=(8, 12), weights=None) -> "_lib.PcgrlLoderunnerC
     return cfg
 
 
-class LodeRunnerEvaluator:
+class LodeRunnerEvaluator(MeasuresMixin):
     """Evaluates batches of Lode Runner maps on one device.  Owns the search workspace, a torch tensor sized at the first
     evaluate() for the launch it needs (pcgrl_loderunner_workspace_bytes(min(n, max_levels), H, W) bytes: one slot per block of
     the launch -- 150 KiB per level at 8 x 12 up to 4096 levels, 598 MiB; never more than 640 MiB) and grown when a larger batch
@@ -246,21 +246,8 @@ class LodeRunnerEvaluator:
         if bits & 1:
             raise ValueError("loderunner: a tile id above 7 was seen on the device (read as empty)")
 
-    _entropy_tab = None  # built at the first measures(entropy=True)
-
-    def _entropy_table(self):
-        """tab[c] = (c / n) * ln(c / n) for c = 0 .. n, then get_entropy's max_val (evolve.py:436) with T = 8: built once on
-        the host with numpy's scalar log -- the very operations of get_entropy (evolve.py:441-444) -- and uploaded at first use
-        (SmbMeasures._entropy_table with ln 8)"""
-        if self._entropy_tab is None:
-            n, T = self.map_shape[0] * self.map_shape[1], len(LODERUNNER_TILES)
-            tab = np.zeros(n + 2, dtype=np.float64)
-            for c in range(1, n + 1):
-                p = np.int64(c) / n
-                tab[c] = p * np.log(p)
-            tab[n + 1] = -(1 / T) * np.log(1 / T) * T
-            self._entropy_tab = torch.from_numpy(tab).to(self.device)
-        return self._entropy_tab
+    def _meas_dims(self):
+        return self.map_shape[0] * self.map_shape[1], len(LODERUNNER_TILES)
 
     def _grids_arg(self, grids):
         if self._closed:
@@ -282,27 +269,8 @@ class LodeRunnerEvaluator:
         entropy does on the host whose numpy built the table.  The divisors are the map's own H * W.  grids: uint8 [n][H][W] at
         any alignment, n >= 0; ids are masked to 3 bits and set no error.  One launch on the current stream, no host sync."""
         g = self._grids_arg(grids)
-        n, dev, T = g.shape[0], self.device, len(LODERUNNER_TILES)
-        H, W = self.map_shape
-        out = SimpleNamespace(counts=torch.empty((n, T), dtype=torch.int32, device=dev),
-                              match=torch.empty((n, 3), dtype=torch.int32, device=dev),
-                              forms=torch.empty((n, 5 + T), dtype=torch.float64, device=dev),
-                              entropy=torch.empty(n, dtype=torch.float64, device=dev) if entropy else None)
-        ent = out.entropy.data_ptr() if entropy else None
-        tab = self._entropy_table().data_ptr() if entropy else None
-        with torch.cuda.device(dev):
-            _lib.check(self._L.pcgrl_loderunner_measures_for_grids(H, W, n, g.data_ptr(), out.counts.data_ptr(),
-                                                                   out.match.data_ptr(), out.forms.data_ptr(), ent, tab,
-                                                                   self._stream()), "pcgrl_loderunner_measures_for_grids")
-        # the float64 forms come from the kernel (correctly rounded divisions in the reference's order): views of its rows
-        f = out.forms
-        out.tile_fractions = f[:, 5:]  # get_counts (evolve.py:461-464)
-        out.bc = {"emptiness": f[:, 0], "symmetry-horizontal": f[:, 1], "symmetry-vertical": f[:, 2], "symmetry": f[:, 3],
-                  "co-occurance": f[:, 4]}
-        if entropy:
-            out.bc["entropy"] = out.entropy
-        out.emptiness = out.bc["emptiness"]
-        return out
+        H, W, n = *self.map_shape, g.shape[0]
+        return self._measures_result(self._L.pcgrl_loderunner_measures_for_grids, (H, W, n, g.data_ptr()), n, entropy)
 
     def diversity(self, grids, group=None, pairwise=False):
         """Pairwise Hamming distances (cells whose tiles differ) among the maps in consecutive groups of `group` maps (None: one
@@ -311,28 +279,9 @@ class LodeRunnerEvaluator:
         (evo/evolve.py:1236-1244) float64 [G], pairwise int32 [G, K, K] or None.  Three launches on the current stream, no host
         sync."""
         g = self._grids_arg(grids)
-        n, dev = g.shape[0], self.device
-        H, W = self.map_shape
-        K = n if group is None else int(group)
-        if K < 2 or n % K:
-            raise ValueError(f"diversity: group = {K} must be at least 2 and divide the {n} maps")
-        G = n // K
-        nbytes = int(self._L.pcgrl_loderunner_diversity_scratch_bytes(H, W, n))
-        scratch = torch.empty(max(1, nbytes // 8), dtype=torch.int64, device=dev)
-        out = SimpleNamespace(hamming_sum=torch.empty(G, dtype=torch.int64, device=dev),
-                              scores=torch.empty((G, 2), dtype=torch.float64, device=dev),
-                              nearest=torch.empty(n, dtype=torch.int32, device=dev),
-                              nearest_idx=torch.empty(n, dtype=torch.int32, device=dev),
-                              pairwise=torch.empty((G, K, K), dtype=torch.int32, device=dev) if pairwise else None)
-        pw = out.pairwise.data_ptr() if pairwise else None
-        with torch.cuda.device(dev):
-            _lib.check(self._L.pcgrl_loderunner_diversity_for_grids(H, W, n, g.data_ptr(), K, scratch.data_ptr(),
-                                                                    out.hamming_sum.data_ptr(), out.scores.data_ptr(),
-                                                                    out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw,
-                                                                    self._stream()), "pcgrl_loderunner_diversity_for_grids")
-        out.div_score = out.scores[:, 0]  # div_calc (evaluate_ctrl.py:42-48)
-        out.diversity_bonus = out.scores[:, 1]  # evolve.py:1236-1244: N * N - 1, not N * (N - 1)
-        return out
+        H, W, n = *self.map_shape, g.shape[0]
+        return self._diversity_result(self._L.pcgrl_loderunner_diversity_for_grids, (H, W, n, g.data_ptr()), n, group, pairwise,
+                                      self._L.pcgrl_loderunner_diversity_scratch_bytes(H, W, n))
 
     def behaviour(self, grids, names):
         """The behaviour vector of each map: float64 [n, len(names)], column j the reference's get_bc(names[j], ...)

@@ -6,12 +6,11 @@ This module evaluates maps; smb_env.py steps SMB environments (SmbVecEnv) with t
 engine, so PROBLEMS / problem_spec / build_config do not know "smb".  file:line references are relative to the reference's control_pcgrl/ directory.
 """
 import ctypes as C
-from types import SimpleNamespace
 
-import numpy as np
 import torch
 
 from . import _lib
+from .measures import MeasuresMixin
 from .problems import ProblemSpec, target_interval
 
 SMB_TILES = ["empty", "solid", "enemy", "brick", "question", "coin", "tube"]  # envs/probs/smb/smb_prob.py:12
@@ -57,26 +56,14 @@ def smb_config(map_shape=(16, 116), solver_power=10000, weights=None) -> "_lib.P
     return cfg
 
 
-class SmbMeasures:
+class SmbMeasures(MeasuresMixin):
     """Level measures and pairwise Hamming diversity of Mario maps on the device (include/pcgrl_amd_smb_measures.h, DESIGN.md
     section 24): what SmbEvaluator and SmbVecEnv share.  The result namespaces are field for field those of
     VecPcgrlEnv.measures / .diversity, with T = 7.  A user class has map_shape, device, _L and _stream(); `h` is an env handle
     whose committed maps are read, or None with caller maps."""
 
-    _entropy_tab = None  # built at first use
-
-    def _entropy_table(self):
-        """tab[c] = (c / n) * ln(c / n) for c = 0 .. n, then get_entropy's max_val (evolve.py:436) with T = 7: built once on
-        the host with numpy's scalar log -- the very operations of get_entropy (evolve.py:441-444) -- and uploaded at first use"""
-        if self._entropy_tab is None:
-            n, T = self.map_shape[0] * self.map_shape[1], len(SMB_TILES)
-            tab = np.zeros(n + 2, dtype=np.float64)
-            for c in range(1, n + 1):
-                p = np.int64(c) / n
-                tab[c] = p * np.log(p)
-            tab[n + 1] = -(1 / T) * np.log(1 / T) * T
-            self._entropy_tab = torch.from_numpy(tab).to(self.device)
-        return self._entropy_tab
+    def _meas_dims(self):
+        return self.map_shape[0] * self.map_shape[1], len(SMB_TILES)
 
     def _grids_arg(self, grids):
         g = torch.as_tensor(grids, device=self.device)
@@ -89,60 +76,16 @@ class SmbMeasures:
         return g.contiguous()
 
     def _measures(self, h, n, grids, entropy):
-        dev, T = self.device, len(SMB_TILES)
-        H, W = self.map_shape
-        out = SimpleNamespace(counts=torch.empty((n, T), dtype=torch.int32, device=dev),
-                              match=torch.empty((n, 3), dtype=torch.int32, device=dev),
-                              forms=torch.empty((n, 5 + T), dtype=torch.float64, device=dev),
-                              entropy=torch.empty(n, dtype=torch.float64, device=dev) if entropy else None)
-        ent = out.entropy.data_ptr() if entropy else None
-        tab = self._entropy_table().data_ptr() if entropy else None
-        with torch.cuda.device(dev):
-            if h is not None:
-                _lib.check(self._L.pcgrl_smb_env_measures(h, out.counts.data_ptr(), out.match.data_ptr(), out.forms.data_ptr(),
-                                                          ent, tab, self._stream()), "pcgrl_smb_env_measures")
-            else:
-                _lib.check(self._L.pcgrl_smb_measures_for_grids(H, W, n, grids.data_ptr(), out.counts.data_ptr(),
-                                                                out.match.data_ptr(), out.forms.data_ptr(), ent, tab,
-                                                                self._stream()), "pcgrl_smb_measures_for_grids")
-        # the float64 forms come from the kernel (correctly rounded divisions in the reference's order): views of its rows
-        f = out.forms
-        out.tile_fractions = f[:, 5:]  # get_counts (evolve.py:461-464)
-        out.bc = {"emptiness": f[:, 0], "symmetry-horizontal": f[:, 1], "symmetry-vertical": f[:, 2], "symmetry": f[:, 3],
-                  "co-occurance": f[:, 4]}
-        if entropy:
-            out.bc["entropy"] = out.entropy
-        out.emptiness = out.bc["emptiness"]
-        return out
+        if h is not None:
+            return self._measures_result(self._L.pcgrl_smb_env_measures, (h,), n, entropy)
+        return self._measures_result(self._L.pcgrl_smb_measures_for_grids, (*self.map_shape, n, grids.data_ptr()), n, entropy)
 
     def _diversity(self, h, n, grids, group, pairwise):
-        K = n if group is None else int(group)
-        dev = self.device
-        H, W = self.map_shape
-        if K < 2 or n % K:
-            raise ValueError(f"diversity: group = {K} must be at least 2 and divide the {n} maps")
-        G = n // K
-        scratch = torch.empty(max(1, int(self._L.pcgrl_smb_diversity_scratch_bytes(H, W, n)) // 8), dtype=torch.int64, device=dev)
-        out = SimpleNamespace(hamming_sum=torch.empty(G, dtype=torch.int64, device=dev),
-                              scores=torch.empty((G, 2), dtype=torch.float64, device=dev),
-                              nearest=torch.empty(n, dtype=torch.int32, device=dev),
-                              nearest_idx=torch.empty(n, dtype=torch.int32, device=dev),
-                              pairwise=torch.empty((G, K, K), dtype=torch.int32, device=dev) if pairwise else None)
-        pw = out.pairwise.data_ptr() if pairwise else None
-        with torch.cuda.device(dev):
-            if h is not None:
-                _lib.check(self._L.pcgrl_smb_env_diversity(h, K, scratch.data_ptr(), out.hamming_sum.data_ptr(),
-                                                           out.scores.data_ptr(), out.nearest.data_ptr(),
-                                                           out.nearest_idx.data_ptr(), pw, self._stream()),
-                           "pcgrl_smb_env_diversity")
-            else:
-                _lib.check(self._L.pcgrl_smb_diversity_for_grids(H, W, n, grids.data_ptr(), K, scratch.data_ptr(),
-                                                                 out.hamming_sum.data_ptr(), out.scores.data_ptr(),
-                                                                 out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw,
-                                                                 self._stream()), "pcgrl_smb_diversity_for_grids")
-        out.div_score = out.scores[:, 0]  # div_calc (evaluate_ctrl.py:42-48)
-        out.diversity_bonus = out.scores[:, 1]  # evolve.py:1236-1244: N * N - 1, not N * (N - 1)
-        return out
+        fn, head = self._L.pcgrl_smb_env_diversity, (h,)
+        if h is None:
+            fn, head = self._L.pcgrl_smb_diversity_for_grids, (*self.map_shape, n, grids.data_ptr())
+        return self._diversity_result(fn, head, n, group, pairwise,
+                                      self._L.pcgrl_smb_diversity_scratch_bytes(*self.map_shape, n))
 
 
 class SmbEvaluator(SmbMeasures):

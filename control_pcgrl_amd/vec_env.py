@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .measures import MeasuresMixin
 from .problems import PROBLEMS, REPRESENTATIONS, problem_spec, target_interval
 
 
@@ -166,7 +167,7 @@ def _codes_from_scratch(env, out_ptr, stream):
     return env._L.pcgrl_onehot_to_codes(env._h, env._via, env.num_envs, out_ptr, stream)
 
 
-class VecPcgrlEnv:
+class VecPcgrlEnv(MeasuresMixin):
     """N independent PCGRL envs on one GPU.
 
     step(actions) -> (obs uint8 [N, *obs_shape], reward f32 [N], done bool [N], truncated bool [N], info)
@@ -208,7 +209,6 @@ class VecPcgrlEnv:
         _lib.check(L.pcgrl_create(C.byref(self.cfg), self.num_envs, dev_index, C.byref(h)), "pcgrl_create")
         self._h = h
         self._L = L
-        self._entropy_tab = None  # measures(): built at first use
         self._dev_index = dev_index
         shape = (C.c_int32 * 4)()
         nd = C.c_int32()
@@ -697,18 +697,10 @@ class VecPcgrlEnv:
         return self._solutions(g.numel() // self.n_cells, g, cap, dist_win)
 
     # -- level measures and pairwise Hamming diversity (include/pcgrl_amd_measures.h) ------------------------------------
-    def _entropy_table(self):
-        """tab[c] = (c / n) * ln(c / n) for c = 0 .. n, then get_entropy's max_val (evolve.py:436): built once per engine on
-        the host with numpy's scalar log -- the very operations of get_entropy (evolve.py:441-444) -- and uploaded at first use"""
-        if self._entropy_tab is None:
-            n, T = self.n_cells, self.spec.n_tiles
-            tab = np.zeros(n + 2, dtype=np.float64)
-            for c in range(1, n + 1):
-                p = np.int64(c) / n
-                tab[c] = p * np.log(p)
-            tab[n + 1] = -(1 / T) * np.log(1 / T) * T
-            self._entropy_tab = torch.from_numpy(tab).to(self.device)
-        return self._entropy_tab
+    _meas_set_device = False  # (every entry point takes the handle and sets its device)
+
+    def _meas_dims(self):
+        return self.n_cells, self.spec.n_tiles
 
     def _measures_supported(self):
         if len(self.map_shape) != 2:  # (the entry point refuses the 3-D maze before it looks at its pointers: its reason)
@@ -716,30 +708,9 @@ class VecPcgrlEnv:
 
     def _measures(self, n, grids, entropy):
         self._measures_supported()
-        dev, T = self.device, self.spec.n_tiles
-        out = SimpleNamespace(counts=torch.empty((n, T), dtype=torch.int32, device=dev),
-                              match=torch.empty((n, 3), dtype=torch.int32, device=dev),
-                              forms=torch.empty((n, 5 + T), dtype=torch.float64, device=dev),
-                              entropy=torch.empty(n, dtype=torch.float64, device=dev) if entropy else None)
-        ent = out.entropy.data_ptr() if entropy else None
-        tab = self._entropy_table().data_ptr() if entropy else None
         if grids is None:
-            _lib.check(self._L.pcgrl_measures(self._h, out.counts.data_ptr(), out.match.data_ptr(), out.forms.data_ptr(), ent, tab,
-                                              self._stream()), "pcgrl_measures")
-        else:
-            _lib.check(self._L.pcgrl_measures_for_grids(self._h, n, grids.data_ptr(), out.counts.data_ptr(),
-                                                        out.match.data_ptr(), out.forms.data_ptr(), ent, tab, self._stream()),
-                       "pcgrl_measures_for_grids")
-        # the float64 forms come from the kernel (correctly rounded divisions in the reference's order; torch's division by
-        # a scalar multiplies by its reciprocal, which is an ulp off now and then): views of its rows
-        f = out.forms
-        out.tile_fractions = f[:, 5:]  # get_counts (evolve.py:461-464)
-        out.bc = {"emptiness": f[:, 0], "symmetry-horizontal": f[:, 1], "symmetry-vertical": f[:, 2], "symmetry": f[:, 3],
-                  "co-occurance": f[:, 4]}
-        if entropy:
-            out.bc["entropy"] = out.entropy
-        out.emptiness = out.bc["emptiness"]
-        return out
+            return self._measures_result(self._L.pcgrl_measures, (self._h,), n, entropy)
+        return self._measures_result(self._L.pcgrl_measures_for_grids, (self._h, n, grids.data_ptr()), n, entropy)
 
     def measures(self, entropy=True):
         """The behaviour characteristics of every env's current map that the reference computes from the integer map
@@ -760,30 +731,10 @@ class VecPcgrlEnv:
 
     def _diversity(self, n, grids, group, pairwise):
         self._measures_supported()
-        K = n if group is None else int(group)
-        dev = self.device
-        if K < 2 or n % K:
-            raise ValueError(f"diversity: group = {K} must be at least 2 and divide the {n} maps")
-        G = n // K
-        scratch = torch.empty(max(1, int(self._L.pcgrl_diversity_scratch_bytes(self._h, n)) // 8), dtype=torch.int64, device=dev)
-        out = SimpleNamespace(hamming_sum=torch.empty(G, dtype=torch.int64, device=dev),
-                              scores=torch.empty((G, 2), dtype=torch.float64, device=dev),
-                              nearest=torch.empty(n, dtype=torch.int32, device=dev),
-                              nearest_idx=torch.empty(n, dtype=torch.int32, device=dev),
-                              pairwise=torch.empty((G, K, K), dtype=torch.int32, device=dev) if pairwise else None)
-        pw = out.pairwise.data_ptr() if pairwise else None
-        if grids is None:
-            _lib.check(self._L.pcgrl_diversity(self._h, K, scratch.data_ptr(), out.hamming_sum.data_ptr(), out.scores.data_ptr(),
-                                               out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw, self._stream()),
-                       "pcgrl_diversity")
-        else:
-            _lib.check(self._L.pcgrl_diversity_for_grids(self._h, n, grids.data_ptr(), K, scratch.data_ptr(),
-                                                         out.hamming_sum.data_ptr(), out.scores.data_ptr(),
-                                                         out.nearest.data_ptr(), out.nearest_idx.data_ptr(), pw, self._stream()),
-                       "pcgrl_diversity_for_grids")
-        out.div_score = out.scores[:, 0]  # div_calc (evaluate_ctrl.py:42-48)
-        out.diversity_bonus = out.scores[:, 1]  # evolve.py:1236-1244: N * N - 1, not N * (N - 1)
-        return out
+        fn, head = self._L.pcgrl_diversity, (self._h,)
+        if grids is not None:
+            fn, head = self._L.pcgrl_diversity_for_grids, (self._h, n, grids.data_ptr())
+        return self._diversity_result(fn, head, n, group, pairwise, self._L.pcgrl_diversity_scratch_bytes(self._h, n))
 
     def diversity(self, group=None, pairwise=False):
         """Pairwise Hamming distances (cells whose tiles differ) among the envs' current maps, in consecutive groups of `group`
