@@ -57,6 +57,8 @@
 #include "loderunner/pcgrl_loderunner_routes.h"  // the routes behind path-length
 #include "../../include/pcgrl_amd_loderunner_measures.h"
 #include "loderunner/pcgrl_loderunner_measures.h"  // level measures and pairwise Hamming diversity of Lode Runner maps
+#include "../../include/pcgrl_amd_microstructure.h"
+#include "microstructure/pcgrl_microstructure.h"  // microstructure levels: path-length, tortuosity, measures
 
 using namespace pcgrl;
 
@@ -2361,6 +2363,77 @@ int pcgrl_loderunner_diversity_for_grids(int32_t h, int32_t w, int32_t n, const 
   if (rc == PCGRL_OK) rc = lr_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
   return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), LR_MEAS_PLANES, launch_lr_measures, group, d_scratch, d_sum,
+                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- microstructure levels
+// include/pcgrl_amd_microstructure.h; kernels in microstructure/pcgrl_microstructure.h.  No handle and no workspace.  The
+// measures and the diversity are the (2, 1, 4096) instantiation of the wave body through the host path of "measures and
+// diversity" above.
+static int ms_check_shape(const char *who, int32_t h, int32_t w) {
+  if (h < 1 || h > MS_MAX_H || w < 1 || w > MS_MAX_W)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..64 rows and 1..64 columns only");
+  return PCGRL_OK;
+}
+
+extern "C" {
+
+int pcgrl_microstructure_evaluate(const pcgrl_microstructure_config *cfg, int32_t n, const uint8_t *d_grids, int32_t region_cap,
+                                  double *d_stats, double *d_loss, int32_t *d_regions, int16_t *d_region_rec,
+                                  double *d_region_tort, uint32_t *d_error, void *stream) {
+  const char *who = "pcgrl_microstructure_evaluate";
+  if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (region_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": region_cap must not be negative");
+  const int rc = ms_check_shape(who, cfg->h, cfg->w);
+  if (rc != PCGRL_OK) return rc;
+  MsArgs a{};
+  a.h = cfg->h;
+  a.w = cfg->w;
+  a.n = n;
+  a.grids = d_grids;
+  a.region_cap = region_cap;
+  a.stats = d_stats;
+  a.loss = d_loss;
+  a.regions = d_regions;
+  a.region_rec = region_cap > 0 ? d_region_rec : nullptr;
+  a.region_tort = region_cap > 0 ? d_region_tort : nullptr;
+  a.error = d_error;
+  for (int k = 0; k < MS_STATS; k++) {
+    a.has_trg[k] = cfg->has_trg[k];
+    a.weight[k] = cfg->weight[k];
+    a.trg_lo[k] = cfg->trg_lo[k];
+    a.trg_hi[k] = cfg->trg_hi[k];
+  }
+  HIPCHK(launch_microstructure(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_microstructure_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
+                                            int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
+                                            void *stream) {
+  const char *who = "pcgrl_microstructure_measures_for_grids";
+  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
+  if (rc == PCGRL_OK) rc = ms_check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_ms_measures, d_counts, d_match, d_forms, d_entropy,
+                          d_entropy_tab, stream);
+}
+
+size_t pcgrl_microstructure_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
+  if (n <= 0 || h < 1 || h > MS_MAX_H || w < 1 || w > MS_MAX_W) return 0;
+  return diversity_scratch_bytes(MS_MEAS_PLANES, h, w, n);
+}
+
+int pcgrl_microstructure_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
+                                             void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
+                                             int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  const char *who = "pcgrl_microstructure_diversity_for_grids";
+  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
+  if (rc == PCGRL_OK) rc = ms_check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), MS_MEAS_PLANES, launch_ms_measures, group, d_scratch, d_sum,
                            d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
