@@ -25,6 +25,10 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
                            0.5 and 0, then BFS) and the returned action list of a batch of maps in one launch; reward() and
                            episode_over() of the problem (ddave_spec() has its tables); measures(), diversity() and
                            behaviour() under the names of DDAVE_BC_NAMES
+  MDungeonEvaluator        MiniDungeon levels: the eleven statistics, the four-stage solver play-through (health, potions,
+                           treasures, goblins and ogres; A* at balance 1, 0.5 and 0, then BFS) and the returned move list of a
+                           batch of maps in one launch; reward() and episode_over() of the problem (mdungeon_spec() has its
+                           tables); measures(), diversity() and behaviour() under the names of MDUNGEON_BC_NAMES
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of
@@ -43,5 +47,6 @@ from .smb_rllib import SmbVectorEnv, make_vector_env  # noqa: F401
 from .loderunner import LODERUNNER_BC_NAMES, LodeRunnerEvaluator, loderunner_spec  # noqa: F401
 from .microstructure import MICROSTRUCTURE_BC_NAMES, MicrostructureEvaluator, microstructure_spec  # noqa: F401
 from .ddave import DDAVE_BC_NAMES, DDaveEvaluator, ddave_spec  # noqa: F401
+from .mdungeon import MDUNGEON_BC_NAMES, MDungeonEvaluator, mdungeon_spec  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

@@ -18,14 +18,16 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "smb/pcgrl_k_smb_state.hip", "smb/pcgrl_k_smb_rollout.hip", "smb/pcgrl_k_smb_vector.hip",
          "smb/pcgrl_k_smb_measures.hip", "loderunner/pcgrl_k_loderunner.hip",
          "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip",
-         "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip"]
+         "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip",
+         "mdungeon/pcgrl_k_mdungeon.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
            "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h", "smb/pcgrl_smb_state.h",
            "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
-           "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h"]
+           "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h",
+           "mdungeon/pcgrl_mdungeon.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -47,6 +49,7 @@ LODERUNNER_MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pc
 LODERUNNER_ROUTES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner_routes.h")
 MICROSTRUCTURE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_microstructure.h")
 DDAVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_ddave.h")
+MDUNGEON_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mdungeon.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -351,6 +354,30 @@ DDAVE_SYMBOLS = {
     "pcgrl_ddave_diversity_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "pcgrl_ddave_diversity_for_grids": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
 }
+# include/pcgrl_amd_mdungeon.h: MiniDungeon levels (statistics and the four-stage play-through; the level measures and pairwise
+# Hamming diversity of such maps; no engine handle)
+PCGRL_MDUNGEON_STATS = 11
+PCGRL_MDUNGEON_WEIGHTS = 9
+PCGRL_MDUNGEON_PLAY = 12
+
+
+class PcgrlMdungeonConfig(C.Structure):
+    _fields_ = [
+        ("h", C.c_int32), ("w", C.c_int32), ("solver_power", C.c_int32), ("max_enemies", C.c_int32),
+        ("max_potions", C.c_int32), ("max_treasures", C.c_int32), ("target_solution", C.c_int32),
+        ("target_col_enemies", C.c_double), ("weight", C.c_double * PCGRL_MDUNGEON_WEIGHTS),
+    ]
+
+
+MDUNGEON_SYMBOLS = {
+    "pcgrl_mdungeon_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "pcgrl_mdungeon_evaluate": (C.c_int, [C.POINTER(PcgrlMdungeonConfig), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int32] + [C.c_void_p] * 6),
+    "pcgrl_mdungeon_measures_for_grids": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "pcgrl_mdungeon_diversity_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "pcgrl_mdungeon_diversity_for_grids": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+                                           + [C.c_void_p] * 7),
+}
 
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
@@ -364,7 +391,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                                                        SMB_ROLLOUT_HEADER, SMB_CTRL_HEADER, SMB_VECTOR_HEADER,
                                                        SMB_MEASURES_HEADER, LODERUNNER_HEADER,
                                                        LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER,
-                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER]
+                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -381,7 +408,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(SMB_VECTOR_HEADER), os.path.getmtime(SMB_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_ROUTES_HEADER), os.path.getmtime(MICROSTRUCTURE_HEADER),
-                   os.path.getmtime(DDAVE_HEADER))
+                   os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -434,7 +461,7 @@ def lib():
                                   + list(SMB_VECTOR_SYMBOLS.items()) + list(SMB_MEASURES_SYMBOLS.items())
                                   + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())
                                   + list(LODERUNNER_ROUTES_SYMBOLS.items()) + list(MICROSTRUCTURE_SYMBOLS.items())
-                                  + list(DDAVE_SYMBOLS.items())):
+                                  + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

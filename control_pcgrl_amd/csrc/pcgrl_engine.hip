@@ -61,6 +61,8 @@
 #include "microstructure/pcgrl_microstructure.h"  // microstructure levels: path-length, tortuosity, measures
 #include "../../include/pcgrl_amd_ddave.h"
 #include "ddave/pcgrl_ddave.h"  // Dangerous Dave levels: statistics and the four-stage play-through, measures
+#include "../../include/pcgrl_amd_mdungeon.h"
+#include "mdungeon/pcgrl_mdungeon.h"  // MiniDungeon levels: statistics and the four-stage play-through, measures
 
 using namespace pcgrl;
 
@@ -2523,6 +2525,95 @@ int pcgrl_ddave_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8
   if (rc == PCGRL_OK) rc = dd_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
   return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), DD_MEAS_PLANES, launch_dd_measures, group, d_scratch, d_sum,
+                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- MiniDungeon levels
+// include/pcgrl_amd_mdungeon.h; kernels in mdungeon/pcgrl_mdungeon.h.  No handle, as for the Dangerous Dave levels above.  The
+// measures and the diversity are the (8, 3, 512) instantiation of the wave body through the host path of "measures and
+// diversity" above.
+static int md_check_shape(const char *who, int32_t h, int32_t w) {
+  if (h < 1 || h > MD_MAX_H || w < 1 || w > MD_MAX_W)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..16 rows and 1..32 columns only");
+  return PCGRL_OK;
+}
+
+static int md_check_power(const char *who, int32_t power) {
+  if (power < 1 || power > MD_MAX_POWER)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": solver_power must be in [1, " + std::to_string(MD_MAX_POWER) + "]");
+  return PCGRL_OK;
+}
+
+extern "C" {
+
+int64_t pcgrl_mdungeon_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t solver_power) {
+  const char *who = "pcgrl_mdungeon_workspace_bytes";
+  if (n < 1) {
+    fail(PCGRL_EINVAL, std::string(who) + ": n must be at least 1");
+    return -1;
+  }
+  if (md_check_shape(who, h, w) != PCGRL_OK || md_check_power(who, solver_power) != PCGRL_OK) return -1;
+  return (int64_t)n * md_ws_stride(solver_power);
+}
+
+int pcgrl_mdungeon_evaluate(const pcgrl_mdungeon_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
+                            int64_t workspace_bytes, int32_t move_cap, int32_t *d_stats, int8_t *d_moves, int32_t *d_length,
+                            int32_t *d_play, uint32_t *d_error, void *stream) {
+  const char *who = "pcgrl_mdungeon_evaluate";
+  if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (move_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": move_cap must not be negative");
+  int rc = md_check_shape(who, cfg->h, cfg->w);
+  if (rc == PCGRL_OK) rc = md_check_power(who, cfg->solver_power);
+  if (rc != PCGRL_OK) return rc;
+  const int64_t stride = md_ws_stride(cfg->solver_power);
+  if (!d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < (int64_t)n * stride)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than "
+                                                 "pcgrl_mdungeon_workspace_bytes");
+  MdArgs a{};
+  a.h = cfg->h;
+  a.w = cfg->w;
+  a.power = cfg->solver_power;
+  a.n = n;
+  a.grids = d_grids;
+  a.ws = (uint8_t *)d_workspace;
+  a.ws_stride = stride;
+  a.hash_cap = md_hash_cap(cfg->solver_power);
+  a.cap = move_cap;
+  a.stats = d_stats;
+  a.moves = move_cap > 0 ? d_moves : nullptr;
+  a.length = d_length;
+  a.play = d_play;
+  a.error = d_error;
+  HIPCHK(launch_mdungeon(a, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_mdungeon_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
+                                      int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
+                                      void *stream) {
+  const char *who = "pcgrl_mdungeon_measures_for_grids";
+  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
+  if (rc == PCGRL_OK) rc = md_check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_md_measures, d_counts, d_match, d_forms, d_entropy,
+                          d_entropy_tab, stream);
+}
+
+size_t pcgrl_mdungeon_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
+  if (n <= 0 || h < 1 || h > MD_MAX_H || w < 1 || w > MD_MAX_W) return 0;
+  return diversity_scratch_bytes(MD_MEAS_PLANES, h, w, n);
+}
+
+int pcgrl_mdungeon_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch,
+                                       int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
+                                       int32_t *d_pairwise, void *stream) {
+  const char *who = "pcgrl_mdungeon_diversity_for_grids";
+  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
+  if (rc == PCGRL_OK) rc = md_check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), MD_MEAS_PLANES, launch_md_measures, group, d_scratch, d_sum,
                            d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
