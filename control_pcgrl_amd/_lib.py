@@ -19,7 +19,7 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "smb/pcgrl_k_smb_measures.hip", "loderunner/pcgrl_k_loderunner.hip",
          "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip",
          "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip",
-         "mdungeon/pcgrl_k_mdungeon.hip"]
+         "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
@@ -27,7 +27,7 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
            "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h",
-           "mdungeon/pcgrl_mdungeon.h"]
+           "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")

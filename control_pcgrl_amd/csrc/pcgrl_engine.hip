@@ -63,6 +63,7 @@
 #include "ddave/pcgrl_ddave.h"  // Dangerous Dave levels: statistics and the four-stage play-through, measures
 #include "../../include/pcgrl_amd_mdungeon.h"
 #include "mdungeon/pcgrl_mdungeon.h"  // MiniDungeon levels: statistics and the four-stage play-through, measures
+#include "step16/pcgrl_step16.h"  // the binary 16x16 step (narrow / turtle, 32x32 window) as a kernel of its own
 
 using namespace pcgrl;
 
@@ -102,6 +103,7 @@ struct pcgrl_engine {
   // kernel, 0 = always step launches, unset = by shape; PCGRL_OBS_NT_MB = observation bytes per launch (MB) from which the
   // stores are non-temporal (default 384, 0 = never)
   int rollout_form = -1;
+  bool step16 = true;  // PCGRL_STEP16=0: the binary 16x16 step stays on step_kernel (A/B runs against step16_kernel, the parity test)
   int rollout_epw = -1;  // PCGRL_ROLLOUT_EPW (development): envs per wavefront of the rollout's simulate role, -1 = chosen by batch size
   // pcgrl_rollout as two kernels (16x16 compile-time kernels, plain mode): the observe role runs on this stream from a
   // snapshot of the pre-call state (tile planes, the scalars of the hot state line, both RNG streams)
@@ -326,8 +328,10 @@ static bool obs_nt_for(const pcgrl_engine *e, int64_t bytes_per_launch) {
 
 // ---------------------------------------------------------------------------------------------- dispatch
 // The kernels live in their own translation units (pcgrl_k_*.hip, see pcgrl_dispatch.h).
-static hipError_t launch(KernelId id, int lpe, const Params &p, size_t lds, hipStream_t s, int cpl = 0) {
+// step16: the engine has not switched step16_kernel off (pcgrl_engine::step16); only the stepping entry points pass it.
+static hipError_t launch(KernelId id, int lpe, const Params &p, size_t lds, hipStream_t s, int cpl = 0, bool step16 = false) {
   const bool wide64 = p.cfg.dims[1] > 32;  // 64-bit row masks (W <= 64); validate() guarantees lpe >= 32 there
+  if (id == K_STEP && step16 && step16_applies(p, lpe)) return launch_step16(p, lds, s);
   switch (p.cfg.problem) {
     case PCGRL_PROB_MC3DMAZE:
       if (p.cfg.representation == PCGRL_REP_TURTLE) return launch_3d_turtle(id, p, cpl, s);
@@ -664,6 +668,8 @@ int pcgrl_create(const pcgrl_config *cfg, int32_t n_envs, int32_t device, pcgrl_
     if (f != nullptr && (f[0] == '0' || f[0] == '1')) e->rollout_form = f[0] - '0';
     if (getenv("PCGRL_OBS_NT_MB")) e->obs_nt_mb = atol(getenv("PCGRL_OBS_NT_MB"));
     if (getenv("PCGRL_ROLLOUT_EPW")) e->rollout_epw = atoi(getenv("PCGRL_ROLLOUT_EPW"));
+    const char *s16 = getenv("PCGRL_STEP16");
+    if (s16 != nullptr && s16[0] == '0') e->step16 = false;
   }
   e->device = device;
   e->lpe = lpe;
@@ -933,7 +939,7 @@ int pcgrl_step(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, uin
   p.reward = d_reward;
   p.done = d_done;
   p.stats_out = d_stats;
-  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
+  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl, h->step16));
   return PCGRL_OK;
 }
 
@@ -969,7 +975,7 @@ int pcgrl_step_ex(pcgrl_handle h, const int32_t *d_actions, int32_t auto_reset, 
   p.done = d_done;
   p.stats_out = d_stats;
   p.ctrl_obs = d_ctrl_obs;
-  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
+  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl, h->step16));
   return PCGRL_OK;
 }
 
@@ -1119,7 +1125,7 @@ int pcgrl_update(pcgrl_handle h, const int32_t *d_actions, uint8_t *d_obs, void 
   p.obs = d_obs;
   p.update_only = 1;
   h->maybe_stale = true;
-  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
+  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl, h->step16));
   return PCGRL_OK;
 }
 
@@ -1630,7 +1636,7 @@ int pcgrl_step_ready(pcgrl_handle h, const int32_t *d_actions, int32_t auto_rese
   p.done = d_done;
   p.stats_out = d_stats;
   p.ready = d_status;
-  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl));
+  HIPCHK(launch(K_STEP, h->lpe, p, h->lds_bytes, (hipStream_t)stream, h->cpl, h->step16));
   return PCGRL_OK;
 }
 
