@@ -19,7 +19,7 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "smb/pcgrl_k_smb_measures.hip", "loderunner/pcgrl_k_loderunner.hip",
          "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip",
          "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip",
-         "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip"]
+         "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip", "archive/pcgrl_k_archive.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
@@ -27,7 +27,7 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
            "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h",
-           "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h"]
+           "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h", "archive/pcgrl_archive.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -50,6 +50,7 @@ LODERUNNER_ROUTES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgr
 MICROSTRUCTURE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_microstructure.h")
 DDAVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_ddave.h")
 MDUNGEON_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mdungeon.h")
+ARCHIVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_archive.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -379,6 +380,25 @@ MDUNGEON_SYMBOLS = {
                                            + [C.c_void_p] * 7),
 }
 
+# include/pcgrl_amd_archive.h: the quality-diversity grid archive (insert, select, mutate; a handle of its own)
+PCGRL_ARCHIVE_MAX_AXES = 4
+PCGRL_ARCHIVE_HEADER_BYTES = 128
+ARCHIVE_SYMBOLS = {
+    "pcgrl_archive_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "pcgrl_archive_destroy": (None, [C.c_void_p]),
+    "pcgrl_archive_add": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8),
+    "pcgrl_archive_cells": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 3),
+    "pcgrl_archive_stats": (C.c_int, [C.c_void_p] * 3),
+    "pcgrl_archive_elites": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    "pcgrl_archive_ask": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_double] + [C.c_void_p] * 3),
+    "pcgrl_archive_state_bytes": (C.c_int64, [C.c_void_p]),
+    "pcgrl_archive_export": (C.c_int, [C.c_void_p] * 3),
+    "pcgrl_archive_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pcgrl_archive_poll_error": (C.c_int, [C.c_void_p] * 2),
+    "pcgrl_archive_last_error": (C.c_char_p, []),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -391,7 +411,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                                                        SMB_ROLLOUT_HEADER, SMB_CTRL_HEADER, SMB_VECTOR_HEADER,
                                                        SMB_MEASURES_HEADER, LODERUNNER_HEADER,
                                                        LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER,
-                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER]
+                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER, ARCHIVE_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -408,7 +428,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(SMB_VECTOR_HEADER), os.path.getmtime(SMB_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_ROUTES_HEADER), os.path.getmtime(MICROSTRUCTURE_HEADER),
-                   os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER))
+                   os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER), os.path.getmtime(ARCHIVE_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -461,7 +481,8 @@ def lib():
                                   + list(SMB_VECTOR_SYMBOLS.items()) + list(SMB_MEASURES_SYMBOLS.items())
                                   + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())
                                   + list(LODERUNNER_ROUTES_SYMBOLS.items()) + list(MICROSTRUCTURE_SYMBOLS.items())
-                                  + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())):
+                                  + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())
+                                  + list(ARCHIVE_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
