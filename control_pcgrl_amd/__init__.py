@@ -29,6 +29,10 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
                            treasures, goblins and ogres; A* at balance 1, 0.5 and 0, then BFS) and the returned move list of a
                            batch of maps in one launch; reward() and episode_over() of the problem (mdungeon_spec() has its
                            tables); measures(), diversity() and behaviour() under the names of MDUNGEON_BC_NAMES
+  Mc3dHoleyEvaluator       3-D holey dungeon and maze levels (an entrance and an exit dug into the border of a cube): the
+                           statistics, the loss and the routes under the player physics of the 3-D maze (walk, step down,
+                           step up, a jump over a gap) of a batch of levels in one launch (mc3d_holey_spec() has the tables);
+                           behaviour() under the statistics' names
   DeviceGridArchive        the quality-diversity grid archive on the device: add() places a batch by its behaviour vectors
                            and keeps each cell's best, ask() draws parents from the occupied cells and mutates them, with no
                            host copy; archive_for(evaluator, names) builds the one the reference's loop would
@@ -51,6 +55,7 @@ from .loderunner import LODERUNNER_BC_NAMES, LodeRunnerEvaluator, loderunner_spe
 from .microstructure import MICROSTRUCTURE_BC_NAMES, MicrostructureEvaluator, microstructure_spec  # noqa: F401
 from .ddave import DDAVE_BC_NAMES, DDaveEvaluator, ddave_spec  # noqa: F401
 from .mdungeon import MDUNGEON_BC_NAMES, MDungeonEvaluator, mdungeon_spec  # noqa: F401
+from .mc3d_holey import Mc3dHoleyEvaluator, all_holes, fixed_holes, mc3d_holey_spec  # noqa: F401
 from .archive import DeviceGridArchive, archive_for  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

@@ -19,7 +19,8 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "smb/pcgrl_k_smb_measures.hip", "loderunner/pcgrl_k_loderunner.hip",
          "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip",
          "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip",
-         "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip", "archive/pcgrl_k_archive.hip"]
+         "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip", "archive/pcgrl_k_archive.hip",
+         "mc3d_holey/pcgrl_k_mc3d_holey.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
@@ -27,7 +28,8 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
            "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h",
-           "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h", "archive/pcgrl_archive.h"]
+           "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h", "archive/pcgrl_archive.h",
+           "mc3d_holey/pcgrl_mc3d_holey.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -51,6 +53,7 @@ MICROSTRUCTURE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_a
 DDAVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_ddave.h")
 MDUNGEON_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mdungeon.h")
 ARCHIVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_archive.h")
+MC3D_HOLEY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mc3d_holey.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -399,6 +402,25 @@ ARCHIVE_SYMBOLS = {
     "pcgrl_archive_last_error": (C.c_char_p, []),
 }
 
+# include/pcgrl_amd_mc3d_holey.h: 3-D holey dungeon and maze levels (statistics, loss and routes; no engine handle)
+PCGRL_MC3D_HOLEY_MAX_STATS = 6
+PCGRL_MC3D_HOLEY_PLAY = 12
+
+
+class PcgrlMc3dHoleyConfig(C.Structure):
+    _fields_ = [
+        ("problem", C.c_int32), ("z", C.c_int32), ("y", C.c_int32), ("x", C.c_int32),
+        ("weight", C.c_double * PCGRL_MC3D_HOLEY_MAX_STATS), ("trg_lo", C.c_double * PCGRL_MC3D_HOLEY_MAX_STATS),
+        ("trg_hi", C.c_double * PCGRL_MC3D_HOLEY_MAX_STATS),
+    ]
+
+
+MC3D_HOLEY_SYMBOLS = {
+    "pcgrl_mc3d_holey_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "pcgrl_mc3d_holey_evaluate": (C.c_int, [C.POINTER(PcgrlMc3dHoleyConfig), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_int32] + [C.c_void_p] * 12),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -411,7 +433,8 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                                                        SMB_ROLLOUT_HEADER, SMB_CTRL_HEADER, SMB_VECTOR_HEADER,
                                                        SMB_MEASURES_HEADER, LODERUNNER_HEADER,
                                                        LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER,
-                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER, ARCHIVE_HEADER]
+                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER, ARCHIVE_HEADER,
+                                                       MC3D_HOLEY_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -428,7 +451,8 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(SMB_VECTOR_HEADER), os.path.getmtime(SMB_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_ROUTES_HEADER), os.path.getmtime(MICROSTRUCTURE_HEADER),
-                   os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER), os.path.getmtime(ARCHIVE_HEADER))
+                   os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER), os.path.getmtime(ARCHIVE_HEADER),
+                   os.path.getmtime(MC3D_HOLEY_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -482,7 +506,7 @@ def lib():
                                   + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())
                                   + list(LODERUNNER_ROUTES_SYMBOLS.items()) + list(MICROSTRUCTURE_SYMBOLS.items())
                                   + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())
-                                  + list(ARCHIVE_SYMBOLS.items())):
+                                  + list(ARCHIVE_SYMBOLS.items()) + list(MC3D_HOLEY_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -332,19 +332,25 @@ def archive_for(evaluator_or_env, names, bins=100, device=None):
     """The archive the reference's loop builds for the behaviour characteristics `names` (evo/evolve.py:1341-1355, :1421-1434):
     `bins` cells per axis; the bounds of a statistic are the problem's cond_bounds and those of the six measure names are
     (0.0, 1.0); map_shape and n_tiles are the evaluator's.  Takes a LodeRunnerEvaluator, SmbEvaluator,
-    MicrostructureEvaluator, DDaveEvaluator, MDungeonEvaluator or a 2-D VecPcgrlEnv."""
+    MicrostructureEvaluator, DDaveEvaluator, MDungeonEvaluator, a 2-D VecPcgrlEnv, or a Mc3dHoleyEvaluator (its map is the
+    Z * Y * X bytes of the interior; its behaviour() takes statistic names only)."""
     from .ddave import DDaveEvaluator
     from .loderunner import LodeRunnerEvaluator
+    from .mc3d_holey import Mc3dHoleyEvaluator
     from .mdungeon import MDungeonEvaluator
     from .microstructure import MicrostructureEvaluator
     from .smb import SmbEvaluator
     from .vec_env import VecPcgrlEnv
     e = evaluator_or_env
-    known = (LodeRunnerEvaluator, SmbEvaluator, MicrostructureEvaluator, DDaveEvaluator, MDungeonEvaluator, VecPcgrlEnv)
+    known = (LodeRunnerEvaluator, SmbEvaluator, MicrostructureEvaluator, DDaveEvaluator, MDungeonEvaluator, VecPcgrlEnv,
+             Mc3dHoleyEvaluator)
     if not isinstance(e, known):
         raise TypeError(f"archive_for takes one of {[k.__name__ for k in known]}, not {type(e).__name__}: it needs the "
                         "problem's cond_bounds, map_shape and tiles")
-    if len(e.map_shape) != 2:
+    if isinstance(e, Mc3dHoleyEvaluator):
+        names = [names] if isinstance(names, str) else list(names)
+        e.check_names(names)
+    elif len(e.map_shape) != 2:
         raise NotImplementedError(f"archive_for: maps of shape {tuple(e.map_shape)} -- the measures and behaviour() exist for "
                                   "2-D maps only")
     return DeviceGridArchive(*archive_shape(e.spec, names, bins), e.map_shape, e.spec.n_tiles,

@@ -63,6 +63,8 @@
 #include "ddave/pcgrl_ddave.h"  // Dangerous Dave levels: statistics and the four-stage play-through, measures
 #include "../../include/pcgrl_amd_mdungeon.h"
 #include "mdungeon/pcgrl_mdungeon.h"  // MiniDungeon levels: statistics and the four-stage play-through, measures
+#include "../../include/pcgrl_amd_mc3d_holey.h"
+#include "mc3d_holey/pcgrl_mc3d_holey.h"  // 3-D holey dungeon and maze levels: statistics, loss and routes
 #include "step16/pcgrl_step16.h"  // the binary 16x16 step (narrow / turtle, 32x32 window) as a kernel of its own
 
 using namespace pcgrl;
@@ -2621,6 +2623,71 @@ int pcgrl_mdungeon_diversity_for_grids(int32_t h, int32_t w, int32_t n, const ui
   if (rc != PCGRL_OK || n == 0) return rc;
   return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), MD_MEAS_PLANES, launch_md_measures, group, d_scratch, d_sum,
                            d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- 3-D holey dungeon and maze levels
+// include/pcgrl_amd_mc3d_holey.h; kernel in mc3d_holey/pcgrl_mc3d_holey.h.  No handle, as for the MiniDungeon levels above.
+static int h3_check_shape(const char *who, int32_t z, int32_t y, int32_t x) {
+  if (z < 3 || z > H3_MAX || y < 3 || y > H3_MAX || x < 3 || x > H3_MAX)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": interiors of 3..16 cells along each axis only");
+  return PCGRL_OK;
+}
+
+extern "C" {
+
+int64_t pcgrl_mc3d_holey_workspace_bytes(int32_t blocks, int32_t z, int32_t y, int32_t x) {
+  const char *who = "pcgrl_mc3d_holey_workspace_bytes";
+  if (blocks < 1) {
+    fail(PCGRL_EINVAL, std::string(who) + ": blocks must be at least 1");
+    return -1;
+  }
+  if (h3_check_shape(who, z, y, x) != PCGRL_OK) return -1;
+  return (int64_t)blocks * h3_ws_stride(h3_cells(z, y, x));
+}
+
+int pcgrl_mc3d_holey_evaluate(const pcgrl_mc3d_holey_config *cfg, int32_t n, const uint8_t *d_grids, const int32_t *d_holes,
+                              void *d_workspace, int64_t workspace_bytes, int32_t route_cap, int32_t *d_stats, double *d_loss,
+                              int32_t *d_play, uint32_t *d_error, int16_t *d_coords, int32_t *d_route_len, int32_t *d_leg_len,
+                              int16_t *d_coords2, int32_t *d_route2_len, uint8_t *d_overlay, uint8_t *d_overlay2, void *stream) {
+  const char *who = "pcgrl_mc3d_holey_evaluate";
+  if (!cfg || !d_grids || !d_holes || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  if (route_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": route_cap must not be negative");
+  if (cfg->problem != PCGRL_MC3D_HOLEY_DUNGEON && cfg->problem != PCGRL_MC3D_HOLEY_MAZE)
+    return fail(PCGRL_EINVAL, std::string(who) + ": problem must be 0 (dungeon) or 1 (maze)");
+  const int rc = h3_check_shape(who, cfg->z, cfg->y, cfg->x);
+  if (rc != PCGRL_OK) return rc;
+  const int cells = h3_cells(cfg->z, cfg->y, cfg->x);
+  const int64_t stride = h3_ws_stride(cells);
+  if (!d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < stride)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than "
+                                                 "pcgrl_mc3d_holey_workspace_bytes(1, z, y, x)");
+  H3Args a{};
+  a.problem = cfg->problem;
+  a.Z = cfg->z, a.Y = cfg->y, a.X = cfg->x;
+  a.n = n;
+  a.grids = d_grids;
+  a.holes = d_holes;
+  a.ws = (uint8_t *)d_workspace;
+  a.ws_stride = stride;
+  a.qcap = h3_qcap(cells);
+  a.route_cap = route_cap;
+  a.stats = d_stats;
+  a.loss = d_loss;
+  a.play = d_play;
+  a.error = d_error;
+  a.coords = route_cap > 0 ? d_coords : nullptr;
+  a.route_len = d_route_len;
+  a.leg_len = d_leg_len;
+  a.coords2 = route_cap > 0 ? d_coords2 : nullptr;
+  a.route2_len = d_route2_len;
+  a.overlay = d_overlay;
+  a.overlay2 = d_overlay2;
+  for (int k = 0; k < H3_MAX_STATS; k++) a.weight[k] = cfg->weight[k], a.trg_lo[k] = cfg->trg_lo[k], a.trg_hi[k] = cfg->trg_hi[k];
+  const int64_t slots = workspace_bytes / stride;
+  HIPCHK(launch_mc3d_holey(a, (int)(slots < n ? slots : n), (hipStream_t)stream));
+  return PCGRL_OK;
 }
 
 }  // extern "C"

@@ -473,7 +473,10 @@ class SmbVecEnv(SmbMeasures):
         each env's control record (active and queued targets, draw counter; not the resampling switch).  One launch, no sync,
         capturable: a captured export writes `out` anew at every replay."""
         if out is None:
-            out = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
+            # with controls the records start at the next multiple of 16: up to 15 bytes before them that the kernel does not
+            # write, so a fresh buffer is zeroed or two images of one state would differ in what the allocator left there
+            alloc = torch.zeros if self.controls else torch.empty
+            out = alloc(self.state_bytes, dtype=torch.uint8, device=self.device)
         elif out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() or out.numel() != self.state_bytes:
             raise ValueError(f"out must be a contiguous uint8 tensor of {self.state_bytes} bytes on {self.device}")
         _lib.check(self._L.pcgrl_smb_state_export(self._handle(), out.data_ptr(), self._stream()), "pcgrl_smb_state_export")
