@@ -19,96 +19,197 @@ constexpr int STEP16_PAIRS = 2;
 typedef uint4 __attribute__((may_alias)) uint4_rec;  // the env record as 16-byte words
 typedef uint2 __attribute__((may_alias)) uint2_rec;
 
-// SWEEP_UNROLL = 6 levels of bfs_level's 16-lane form as ONE asm statement (f0 -> f1 .. f6, each removed from `fr`).  Between
-// two bfs_level statements the compiler has to assume the worst about the hazards at their edges and puts a wait state
-// there; inside one statement the order is known: a frontier is read through DPP three instructions after it was written.
-#define STEP16_LEVEL(in, out)                                                              \
-  "v_lshlrev_b32 %6, 1, " in "\n\t"                                                        \
-  "v_lshrrev_b32 %7, 1, " in "\n\t"                                                        \
-  "v_or_b32_dpp %6, " in ", %6 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"      \
-  "v_or_b32_dpp %7, " in ", %7 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"      \
-  "v_bitop3_b32 " out ", %6, %7, %8 bitop3:0xa8\n\t"                                       \
-  "v_bitop3_b32 %8, %6, %7, %8 bitop3:2\n\t"
-__device__ __attribute__((always_inline)) inline void trip16(uint32_t f0, uint32_t &f1, uint32_t &f2, uint32_t &f3, uint32_t &f4,
-                                                             uint32_t &f5, uint32_t &f6, uint32_t &fr) {
-  uint32_t a, b;
-  asm(STEP16_LEVEL("%9", "%0") STEP16_LEVEL("%0", "%1") STEP16_LEVEL("%1", "%2") STEP16_LEVEL("%2", "%3")
-          STEP16_LEVEL("%3", "%4") STEP16_LEVEL("%4", "%5")
-      : "=&v"(f1), "=&v"(f2), "=&v"(f3), "=&v"(f4), "=&v"(f5), "=&v"(f6), "=&v"(a), "=&v"(b), "+v"(fr)
-      : "v"(f0));
-}
-#undef STEP16_LEVEL
-
-// sweep() for 16 lanes per env and 32-bit masks, without tracked levels.  Every trip runs its SWEEP_UNROLL levels bare.  A
-// group's frontier dies in exactly one trip (a dead frontier stays dead); the frontiers of that trip -- the level it entered
-// the trip with and the first SWEEP_UNROLL - 1 it produced, the last one being empty -- are kept in k[], and its level count
-// at the trip's start in `base`.  Frontiers are non-empty up to the last level and empty from there on, so the group's
-// length is base + the highest index of a non-empty k[], and `last` is that k[].  len, last and visited are sweep()'s:
-// len = number of levels, last = the cells of level len (none when len == 0), visited = everything reached.
-// Which groups are alive is scalar work on the trip's ballot: bit 15 of a group's 16-bit slice stands for "the slice is not
-// zero" ((x & 0x7fff) + 0x7fff carries into bit 15 iff a low bit is set; no carry leaves the slice).
-__device__ __attribute__((always_inline)) inline void sweep16(const Grp<16> &g, uint32_t src, uint32_t avail, int &len,
-                                                              uint32_t &last, uint32_t &visited) {
-  static_assert(SWEEP_UNROLL == 6, "sweep16 keeps six frontiers per trip");
-  constexpr uint64_t LOW = 0x7FFF7FFF7FFF7FFFull, TOP = 0x8000800080008000ull;
-  uint32_t front = src & avail;
-  uint32_t free_cells = avail & ~front;
-  // (a group without a source "dies" in the first trip with six empty frontiers: len 0)
-  uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0, k4 = 0, k5 = 0;
-  int base = 0, lev = 0;
-  uint64_t alive = TOP;
-  while (true) {
-    const uint32_t f0 = front;
-    uint32_t f1, f2, f3, f4, f5;
-    trip16(f0, f1, f2, f3, f4, f5, front, free_cells);
-    const uint64_t bal = __ballot(front != 0);
-    const uint64_t now = (((bal & LOW) + LOW) | bal) & TOP;
-    const uint64_t gone = alive & ~now;
-    if (gone != 0) {  // (wave-uniform; at most once per group and sweep)
-      const bool died = ((gone >> (g.gbase + 15)) & 1ull) != 0;
-      k0 = died ? f0 : k0;
-      k1 = died ? f1 : k1;
-      k2 = died ? f2 : k2;
-      k3 = died ? f3 : k3;
-      k4 = died ? f4 : k4;
-      k5 = died ? f5 : k5;
-      base = died ? lev : base;
-    }
-    lev += SWEEP_UNROLL;
-    alive = now;
-    if (now == 0) break;
+// Per-lane constants of the sweeps: functions of the lane index alone.
+struct Sweep16Lane {
+  uint32_t gbit;   // 1 << (index of the lane's group in the wave): the group's bit in the four-bit alive masks
+  uint32_t rkey;   // 15 - row: ends a key, so that the lowest row wins a max-reduction among equal keys
+  uint32_t below;  // the rows of the group in front of this one, as bits of the group's ballot slice
+  __device__ inline void init(const Grp<16> &g) {
+    gbit = 1u << (g.gbase >> 4);
+    rkey = 15u - (uint32_t)g.row;
+    below = (1u << g.row) - 1u;
   }
-  int myidx = k1 ? 1 : 0;
-  myidx = k2 ? 2 : myidx;
-  myidx = k3 ? 3 : myidx;
-  myidx = k4 ? 4 : myidx;
-  myidx = k5 ? 5 : myidx;
-  const int gidx = (int)g.gmax((uint32_t)myidx);
-  len = base + gidx;
-  uint32_t l = k0;
-  l = gidx == 1 ? k1 : l;
-  l = gidx == 2 ? k2 : l;
-  l = gidx == 3 ? k3 : l;
-  l = gidx == 4 ? k4 : l;
-  l = gidx == 5 ? k5 : l;
-  last = len > 0 ? l : 0u;
-  visited = avail & ~free_cells;
+};
+
+// sweep() for 16 lanes per env and 32-bit masks, without tracked levels, as one asm statement: the trips, their control and
+// the wrap-up.  (Between two statements the compiler has to assume the worst about the hazards at their edges; inside one
+// the order is known: a value is read through DPP, or a compare's mask by a select, at least three instructions after it
+// was written.)
+//
+// A trip is SWEEP_UNROLL = 6 levels of bfs_level's 16-lane form.  A group's frontier dies in exactly one trip (a dead
+// frontier stays dead; a group without a source dies in the first trip with six empty frontiers); the frontiers of that
+// trip -- the level it entered the trip with and the first five it produced, the last one being empty -- are kept in
+// k0..k5, and its level count at the trip's start in `base`.  Frontiers are non-empty up to the last level and empty from
+// there on, so the group's length is base + the highest index of a non-empty k, and `last` is that k.
+//
+// Trip control.  vcc = ballot of the trip's last frontier; two s_quadmask fold it to one bit per group (`now`), the groups
+// that died in this trip are was & ~now, and the branch to the capture block (off the fall-through path, at most once per
+// group and sweep) takes the SCC of that s_andn2.  The loop goes on while vcc != 0.  The body is laid out twice with the two
+// frontier registers and the two mask registers swapped, so nothing is copied and one branch is taken per two trips.
+// `lev` counts levels in units of 16 (96 per trip): base = lev | rkey, and a lane's key is base + 16 * (1 + the highest
+// index of a non-empty k of its own; 0 when it has none).  Keys of a group differ in their last four bits, so ONE
+// max-reduction K gives the length ((K >> 4) - 1; a group without any cell has K < 16 and length 0), the lanes that hold
+// the last level (same key >> 4: a lane has k[gidx] != 0 exactly when its own highest index is gidx) and the first of them
+// in row-major order (key == K); the length is positive exactly when K >= 32.  Each lane has selected its own highest
+// non-empty k meanwhile (`b`), which fills the wait states of the reduction.  Every group dies once, so k0..k5 and base
+// need no initial value.  (The statements are volatile so that they stay between the PHASE_MARKs of the development builds.)
+#define S16_LEVEL(in, out)                                                                   \
+  "v_lshlrev_b32 %[a], 1, " in "\n\t"                                                        \
+  "v_lshrrev_b32 %[b], 1, " in "\n\t"                                                        \
+  "v_or_b32_dpp %[a], " in ", %[a] row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
+  "v_or_b32_dpp %[b], " in ", %[b] row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
+  "v_bitop3_b32 " out ", %[a], %[b], %[fr] bitop3:0xa8\n\t"                                  \
+  "v_bitop3_b32 %[fr], %[a], %[b], %[fr] bitop3:2\n\t"
+#define S16_TRIP(in, out, was, now, cap)                                                                           \
+  S16_LEVEL(in, "%[t1]") S16_LEVEL("%[t1]", "%[t2]") S16_LEVEL("%[t2]", "%[t3]") S16_LEVEL("%[t3]", "%[t4]")       \
+  S16_LEVEL("%[t4]", "%[t5]") S16_LEVEL("%[t5]", out)                                                              \
+  "v_cmp_ne_u32 vcc, 0, " out "\n\t"                                                                               \
+  "s_quadmask_b64 vcc, vcc\n\t"                                                                                    \
+  "s_quadmask_b32 " now ", vcc_lo\n\t"                                                                             \
+  "s_andn2_b32 %[gone], " was ", " now "\n\t"                                                                      \
+  "s_cbranch_scc1 " cap "\n\t"
+#define S16_CAPTURE(in)                                        \
+  "v_and_b32 %[a], %[gone], %[gbit]\n\t"                       \
+  "v_cmp_ne_u32_e64 %[m1], 0, %[a]\n\t"                        \
+  "v_or_b32 %[b], %[lev], %[rkey]\n\t"                         \
+  "s_nop 0\n\t"                                                \
+  "v_cndmask_b32_e64 %[k0], %[k0], " in ", %[m1]\n\t"          \
+  "v_cndmask_b32_e64 %[k1], %[k1], %[t1], %[m1]\n\t"           \
+  "v_cndmask_b32_e64 %[k2], %[k2], %[t2], %[m1]\n\t"           \
+  "v_cndmask_b32_e64 %[k3], %[k3], %[t3], %[m1]\n\t"           \
+  "v_cndmask_b32_e64 %[k4], %[k4], %[t4], %[m1]\n\t"           \
+  "v_cndmask_b32_e64 %[k5], %[k5], %[t5], %[m1]\n\t"           \
+  "v_cndmask_b32_e64 %[base], %[base], %[b], %[m1]\n\t"
+// the loop, then (at .Ls16_done) each lane's key in %[a]; m1..m4 and vcc say which of k1..k5 are non-empty in the lane
+#define S16_SWEEP                                                         \
+  "s_mov_b32 %[ma], 15\n\t"                                               \
+  "s_mov_b32 %[lev], 0\n"                                                 \
+  ".Ls16_a%=:\n\t"                                                        \
+  S16_TRIP("%[fa]", "%[fb]", "%[ma]", "%[mb]", ".Ls16_cap_a%=")           \
+  "\n.Ls16_ra%=:\n\t"                                                     \
+  "s_addk_i32 %[lev], 0x60\n\t"                                           \
+  "s_cbranch_vccz .Ls16_done%=\n\t"                                       \
+  S16_TRIP("%[fb]", "%[fa]", "%[mb]", "%[ma]", ".Ls16_cap_b%=")           \
+  "\n.Ls16_rb%=:\n\t"                                                     \
+  "s_addk_i32 %[lev], 0x60\n\t"                                           \
+  "s_cbranch_vccnz .Ls16_a%=\n\t"                                         \
+  "s_branch .Ls16_done%=\n"                                               \
+  ".Ls16_cap_a%=:\n\t"                                                    \
+  S16_CAPTURE("%[fa]")                                                    \
+  "s_branch .Ls16_ra%=\n"                                                 \
+  ".Ls16_cap_b%=:\n\t"                                                    \
+  S16_CAPTURE("%[fb]")                                                    \
+  "s_branch .Ls16_rb%=\n"                                                 \
+  ".Ls16_done%=:\n\t"                                                     \
+  "v_cmp_ne_u32_e64 %[m1], 0, %[k1]\n\t"                                  \
+  "v_cmp_ne_u32_e64 %[m2], 0, %[k2]\n\t"                                  \
+  "v_cmp_ne_u32_e64 %[m3], 0, %[k3]\n\t"                                  \
+  "v_cmp_ne_u32_e64 %[m4], 0, %[k4]\n\t"                                  \
+  "v_cmp_ne_u32 vcc, 0, %[k5]\n\t"                                        \
+  "v_min_u32 %[a], 1, %[k0]\n\t"                                          \
+  "v_cndmask_b32_e64 %[a], %[a], 2, %[m1]\n\t"                            \
+  "v_cndmask_b32_e64 %[a], %[a], 3, %[m2]\n\t"                            \
+  "v_cndmask_b32_e64 %[a], %[a], 4, %[m3]\n\t"                            \
+  "v_cndmask_b32_e64 %[a], %[a], 5, %[m4]\n\t"                            \
+  "v_cndmask_b32_e64 %[a], %[a], 6, vcc\n\t"                              \
+  "v_lshl_add_u32 %[a], %[a], 4, %[base]\n\t"
+#define S16_OWN(k, m) "v_cndmask_b32_e64 %[b], %[b], " k ", " m "\n\t"
+#define S16_MAX(src, ctrl) "v_max_u32_dpp %[t1], " src ", " src " " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define S16_SUM(ctrl) "v_add_u32_dpp %[sum], %[sum], %[sum] " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define S16_OPERANDS                                                                                                     \
+  [fa] "+v"(fa), [fr] "+v"(free_cells), [fb] "=&v"(fb), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4),  \
+  [t5] "=&v"(t5), [a] "=&v"(a), [b] "=&v"(b), [k0] "=&v"(k0), [k1] "=&v"(k1), [k2] "=&v"(k2), [k3] "=&v"(k3),            \
+  [k4] "=&v"(k4), [k5] "=&v"(k5), [base] "=&v"(base), [ma] "=&s"(ma), [mb] "=&s"(mb), [lev] "=&s"(lev),                  \
+  [gone] "=&s"(gone), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3), [m4] "=&s"(m4)
+
+// The sweep from the single cell `seed` of a component_fars16 piece.  free_cells: in, the cells that may still be reached
+// (without the seed); out, those that were not.  Returns first_rowmajor(g, last): the first cell in row-major order of the
+// last level (none when the sweep has no level at all).
+__device__ __attribute__((always_inline)) inline uint32_t sweep16_far(const Sweep16Lane &c, uint32_t seed, uint32_t &free_cells) {
+  static_assert(SWEEP_UNROLL == 6, "sweep16 keeps six frontiers per trip");
+  uint32_t fa = seed, fb, t1, t2, t3, t4, t5, a, b, k0, k1, k2, k3, k4, k5, base, ma, mb, lev, gone;
+  uint64_t m1, m2, m3, m4;
+  asm volatile(S16_SWEEP
+      "v_cndmask_b32_e64 %[b], %[k0], %[k1], %[m1]\n\t"
+      S16_OWN("%[k2]", "%[m2]")
+      S16_MAX("%[a]", "quad_perm:[1,0,3,2]")
+      S16_OWN("%[k3]", "%[m3]")
+      S16_OWN("%[k4]", "%[m4]")
+      S16_MAX("%[t1]", "quad_perm:[2,3,0,1]")
+      S16_OWN("%[k5]", "vcc")
+      "v_sub_u32 %[t2], 0, %[b]\n\t"
+      S16_MAX("%[t1]", "row_half_mirror")
+      "v_and_b32 %[t2], %[b], %[t2]\n\t"
+      "s_nop 0\n\t"
+      S16_MAX("%[t1]", "row_mirror")
+      "v_cmp_eq_u32_e64 %[m1], %[t1], %[a]\n\t"
+      "v_cmp_lt_u32_e64 %[m2], 31, %[t1]\n\t"
+      "s_and_b64 %[m1], %[m1], %[m2]\n\t"
+      "v_cndmask_b32_e64 %[t3], 0, %[t2], %[m1]"
+      : S16_OPERANDS
+      : [gbit] "v"(c.gbit), [rkey] "v"(c.rkey)
+      : "vcc", "scc");
+  return t3;
 }
 
-// component_fars() on sweep16
-__device__ inline uint32_t component_fars16(const Grp<16> &g, uint32_t comps) {
+// The sweep from all cells of `src` through `avail`: len = number of levels, last = the cells of level len (none when
+// len == 0).  `sum` rides along: in, a value per lane; out, its sum over the group in every lane (gsum's butterfly, whose
+// steps and the max-reduction's fill each other's wait states).
+__device__ __attribute__((always_inline)) inline void sweep16_len(const Sweep16Lane &c, uint32_t src, uint32_t avail, int &len,
+                                                                  uint32_t &last, uint32_t &sum) {
+  uint32_t fa = src & avail, free_cells = avail & ~fa;
+  uint32_t fb, t1, t2, t3, t4, t5, a, b, k0, k1, k2, k3, k4, k5, base, ma, mb, lev, gone;
+  uint64_t m1, m2, m3, m4;
+  asm volatile(S16_SWEEP
+      "v_cndmask_b32_e64 %[b], %[k0], %[k1], %[m1]\n\t"
+      S16_OWN("%[k2]", "%[m2]")
+      S16_MAX("%[a]", "quad_perm:[1,0,3,2]")
+      S16_SUM("quad_perm:[1,0,3,2]")
+      S16_OWN("%[k3]", "%[m3]")
+      S16_MAX("%[t1]", "quad_perm:[2,3,0,1]")
+      S16_SUM("quad_perm:[2,3,0,1]")
+      S16_OWN("%[k4]", "%[m4]")
+      S16_MAX("%[t1]", "row_half_mirror")
+      S16_SUM("row_half_mirror")
+      S16_OWN("%[k5]", "vcc")
+      S16_MAX("%[t1]", "row_mirror")
+      S16_SUM("row_mirror")
+      "v_xor_b32 %[t2], %[t1], %[a]\n\t"
+      "v_cmp_gt_u32_e64 %[m1], 16, %[t2]\n\t"
+      "v_cmp_lt_u32_e64 %[m2], 31, %[t1]\n\t"
+      "s_and_b64 %[m1], %[m1], %[m2]\n\t"
+      "v_max_u32 %[t4], 16, %[t1]\n\t"
+      "v_lshrrev_b32 %[t4], 4, %[t4]\n\t"
+      "v_add_u32 %[t4], -1, %[t4]\n\t"
+      "v_cndmask_b32_e64 %[t3], 0, %[b], %[m1]"
+      : S16_OPERANDS, [sum] "+v"(sum)
+      : [gbit] "v"(c.gbit), [rkey] "v"(c.rkey)
+      : "vcc", "scc");
+  len = (int)t4;
+  last = t3;
+}
+#undef S16_LEVEL
+#undef S16_TRIP
+#undef S16_CAPTURE
+#undef S16_SWEEP
+#undef S16_OWN
+#undef S16_MAX
+#undef S16_SUM
+#undef S16_OPERANDS
+
+// component_fars() on sweep16_far.  The seed of a piece is the lowest cell of the first row of `remaining`: the row whose
+// slice of the ballot has no bit below it.  What a sweep leaves of free_cells is the next `remaining`.
+__device__ inline uint32_t component_fars16(const Grp<16> &g, const Sweep16Lane &c, uint32_t comps) {
   const uint32_t iso = comps & ~expand(g, comps);
   uint32_t remaining = comps & ~iso, fars = iso;
   while (true) {
-    const uint64_t gb = g.gballot(remaining != 0);
-    if (__ballot(gb != 0) == 0) break;
-    const int fl = gb ? __builtin_ctzll(gb) : -1;
-    const uint32_t seed = g.row == fl ? (remaining & (0u - remaining)) : 0u;
-    int depth;
-    uint32_t last, vis;
-    sweep16(g, seed, remaining, depth, last, vis);
-    fars |= first_rowmajor(g, last);
-    remaining &= ~vis;
+    const uint64_t bal = __ballot(remaining != 0);
+    if (bal == 0) break;
+    const uint32_t slice = (uint32_t)(bal >> g.gbase);
+    const uint32_t seed = (slice & c.below) == 0 ? (remaining & (0u - remaining)) : 0u;
+    uint32_t free_cells = remaining ^ seed;
+    fars |= sweep16_far(c, seed, free_cells);
+    remaining = free_cells;
   }
   return fars;
 }
@@ -116,6 +217,8 @@ __device__ inline uint32_t component_fars16(const Grp<16> &g, uint32_t comps) {
 // binary_stats_update() on sweep16: the statistics after editing the single cell `x`
 __device__ inline void binary_stats_update16(const Grp<16> &g, uint32_t x, uint32_t p_old, uint32_t p_new, int &regions,
                                              int &path_len, uint32_t &fars, uint32_t &best PHASE_ARG, bool have_pre, uint32_t pre) {
+  Sweep16Lane c;
+  c.init(g);
   const bool became_pass = g.gany((x & p_new) != 0);
   const bool edited = g.gany(x != 0);
   uint32_t K = edited ? pre : 0u;
@@ -127,21 +230,19 @@ __device__ inline void binary_stats_update16(const Grp<16> &g, uint32_t x, uint3
   const uint32_t touched = K | x;
   const bool hit = g.gany((best & touched) != 0);
   PHASE_MARK(3);  // flood
-  const uint32_t newfars = component_fars16(g, K);
+  const uint32_t newfars = component_fars16(g, c, K);
   PHASE_MARK(4);  // first sweeps
   fars = (fars & ~touched) | newfars;
   int l;
-  uint32_t b, vis;
-  sweep16(g, hit ? fars : newfars, p_new, l, b, vis);
+  uint32_t b, count = (uint32_t)popc_m(fars);  // (summed over the group inside the sweep's wrap-up)
+  sweep16_len(c, hit ? fars : newfars, p_new, l, b, count);
   PHASE_MARK(5);  // second sweep
   if (edited) {
-    regions = (int)g.gsum((uint32_t)popc_m(fars));
+    regions = (int)count;
     if (hit || l > path_len) {
       path_len = l;
       best = b;
     }
-  } else {
-    (void)g.gsum(0u);  // keep the cross-lane reduction in uniform control flow
   }
 }
 
