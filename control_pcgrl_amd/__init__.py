@@ -36,6 +36,9 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   DeviceGridArchive        the quality-diversity grid archive on the device: add() places a batch by its behaviour vectors
                            and keeps each cell's best, ask() draws parents from the occupied cells and mutates them, with no
                            host copy; archive_for(evaluator, names) builds the one the reference's loop would
+  NcaGenerator             the NCA level generator (the reference's default `--model NCA --representation cellular`): G
+                           genomes x S seeds rolled out to their final maps in one launch, bit for bit the numpy twins of
+                           control_pcgrl_amd.nca; generator_for(evaluator_or_env) builds the one for an evaluator's maps
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of
@@ -57,5 +60,7 @@ from .ddave import DDAVE_BC_NAMES, DDaveEvaluator, ddave_spec  # noqa: F401
 from .mdungeon import MDUNGEON_BC_NAMES, MDungeonEvaluator, mdungeon_spec  # noqa: F401
 from .mc3d_holey import Mc3dHoleyEvaluator, all_holes, fixed_holes, mc3d_holey_spec  # noqa: F401
 from .archive import DeviceGridArchive, archive_for  # noqa: F401
+from . import nca  # noqa: F401
+from .nca import NcaGenerator, generator_for  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number

@@ -20,7 +20,7 @@ UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pc
          "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip",
          "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip",
          "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip", "archive/pcgrl_k_archive.hip",
-         "mc3d_holey/pcgrl_k_mc3d_holey.hip"]
+         "mc3d_holey/pcgrl_k_mc3d_holey.hip", "nca/pcgrl_k_nca.hip"]
 HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
            "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
            "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
@@ -29,7 +29,7 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
            "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h",
            "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h", "archive/pcgrl_archive.h",
-           "mc3d_holey/pcgrl_mc3d_holey.h"]
+           "mc3d_holey/pcgrl_mc3d_holey.h", "nca/pcgrl_nca.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -54,6 +54,7 @@ DDAVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_ddave.
 MDUNGEON_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mdungeon.h")
 ARCHIVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_archive.h")
 MC3D_HOLEY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mc3d_holey.h")
+NCA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_nca.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -421,6 +422,16 @@ MC3D_HOLEY_SYMBOLS = {
                                             C.c_int64, C.c_int32] + [C.c_void_p] * 12),
 }
 
+# include/pcgrl_amd_nca.h: the NCA level generator (genomes x seeds rolled out in one launch; a handle of its own)
+NCA_SYMBOLS = {
+    "pcgrl_nca_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "pcgrl_nca_destroy": (None, [C.c_void_p]),
+    "pcgrl_nca_generate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+                           + [C.c_void_p] * 4),
+    "pcgrl_nca_poll_error": (C.c_int, [C.c_void_p] * 2),
+    "pcgrl_nca_last_error": (C.c_char_p, []),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -434,7 +445,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                                                        SMB_MEASURES_HEADER, LODERUNNER_HEADER,
                                                        LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER,
                                                        MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER, ARCHIVE_HEADER,
-                                                       MC3D_HOLEY_HEADER]
+                                                       MC3D_HOLEY_HEADER, NCA_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -452,7 +463,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_ROUTES_HEADER), os.path.getmtime(MICROSTRUCTURE_HEADER),
                    os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER), os.path.getmtime(ARCHIVE_HEADER),
-                   os.path.getmtime(MC3D_HOLEY_HEADER))
+                   os.path.getmtime(MC3D_HOLEY_HEADER), os.path.getmtime(NCA_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -506,7 +517,8 @@ def lib():
                                   + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())
                                   + list(LODERUNNER_ROUTES_SYMBOLS.items()) + list(MICROSTRUCTURE_SYMBOLS.items())
                                   + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())
-                                  + list(ARCHIVE_SYMBOLS.items()) + list(MC3D_HOLEY_SYMBOLS.items())):
+                                  + list(ARCHIVE_SYMBOLS.items()) + list(MC3D_HOLEY_SYMBOLS.items())
+                                  + list(NCA_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
