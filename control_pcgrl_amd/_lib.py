@@ -27,9 +27,9 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h", "smb/pcgrl_smb_state.h",
            "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
-           "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h", "ddave/pcgrl_ddave.h",
-           "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h", "archive/pcgrl_archive.h",
-           "mc3d_holey/pcgrl_mc3d_holey.h", "nca/pcgrl_nca.h"]
+           "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h",
+           "playthrough/pcgrl_playthrough.h", "ddave/pcgrl_ddave.h", "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h",
+           "archive/pcgrl_archive.h", "mc3d_holey/pcgrl_mc3d_holey.h", "nca/pcgrl_nca.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")

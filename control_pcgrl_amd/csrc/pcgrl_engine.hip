@@ -2451,70 +2451,84 @@ int pcgrl_microstructure_diversity_for_grids(int32_t h, int32_t w, int32_t n, co
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------------------- Dangerous Dave levels
-// include/pcgrl_amd_ddave.h; kernels in ddave/pcgrl_ddave.h.  No handle, as for the Mario levels above.  The measures and the
-// diversity are the (7, 3, 512) instantiation of the wave body through the host path of "measures and diversity" above.
-static int dd_check_shape(const char *who, int32_t h, int32_t w) {
-  if (h < 1 || h > DD_MAX_H || w < 1 || w > DD_MAX_W)
+// ---------------------------------------------------------------------------------------------- solver play-throughs
+// What the entry points of the Dangerous Dave and MiniDungeon levels below share (playthrough/pcgrl_playthrough.h): `who` names
+// the caller in the error text, `ws_name` the function whose size the workspace must have, `launch` is the game's kernel.
+static int pt_check_shape(const char *who, int32_t h, int32_t w) {
+  if (h < 1 || h > PT_MAX_H || w < 1 || w > PT_MAX_W)
     return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..16 rows and 1..32 columns only");
   return PCGRL_OK;
 }
 
-static int dd_check_power(const char *who, int32_t power) {
-  if (power < 1 || power > DD_MAX_POWER)
-    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": solver_power must be in [1, " + std::to_string(DD_MAX_POWER) + "]");
+static int pt_check_power(const char *who, int32_t power) {
+  if (power < 1 || power > PT_MAX_POWER)
+    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": solver_power must be in [1, " + std::to_string(PT_MAX_POWER) + "]");
   return PCGRL_OK;
 }
 
-extern "C" {
-
-int64_t pcgrl_ddave_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t solver_power) {
-  const char *who = "pcgrl_ddave_workspace_bytes";
+static int64_t pt_workspace_bytes(const char *who, int32_t n, int32_t h, int32_t w, int32_t power) {
   if (n < 1) {
     fail(PCGRL_EINVAL, std::string(who) + ": n must be at least 1");
     return -1;
   }
-  if (dd_check_shape(who, h, w) != PCGRL_OK || dd_check_power(who, solver_power) != PCGRL_OK) return -1;
-  return (int64_t)n * dd_ws_stride(solver_power);
+  if (pt_check_shape(who, h, w) != PCGRL_OK || pt_check_power(who, power) != PCGRL_OK) return -1;
+  return (int64_t)n * pt_ws_stride(power);
 }
 
-int pcgrl_ddave_evaluate(const pcgrl_ddave_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
-                         int64_t workspace_bytes, int32_t move_cap, int32_t *d_stats, int8_t *d_moves, int32_t *d_length,
-                         int32_t *d_play, uint32_t *d_error, void *stream) {
-  const char *who = "pcgrl_ddave_evaluate";
-  if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+static int pt_evaluate(const char *who, const char *ws_name, hipError_t (*launch)(const PtArgs &, hipStream_t), int32_t h,
+                       int32_t w, int32_t power, int32_t n, const uint8_t *d_grids, void *d_workspace, int64_t workspace_bytes,
+                       int32_t move_cap, int32_t *d_stats, int8_t *d_moves, int32_t *d_length, int32_t *d_play,
+                       uint32_t *d_error, void *stream) {
+  if (!d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
   if (move_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": move_cap must not be negative");
-  int rc = dd_check_shape(who, cfg->h, cfg->w);
-  if (rc == PCGRL_OK) rc = dd_check_power(who, cfg->solver_power);
+  int rc = pt_check_shape(who, h, w);
+  if (rc == PCGRL_OK) rc = pt_check_power(who, power);
   if (rc != PCGRL_OK) return rc;
-  const int64_t stride = dd_ws_stride(cfg->solver_power);
+  const int64_t stride = pt_ws_stride(power);
   if (!d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < (int64_t)n * stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than "
-                                                 "pcgrl_ddave_workspace_bytes");
-  DdArgs a{};
-  a.h = cfg->h;
-  a.w = cfg->w;
-  a.power = cfg->solver_power;
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than " + ws_name);
+  PtArgs a{};
+  a.h = h;
+  a.w = w;
+  a.power = power;
   a.n = n;
   a.grids = d_grids;
   a.ws = (uint8_t *)d_workspace;
   a.ws_stride = stride;
-  a.hash_cap = dd_hash_cap(cfg->solver_power);
+  a.hash_cap = pt_hash_cap(power);
   a.cap = move_cap;
   a.stats = d_stats;
   a.moves = move_cap > 0 ? d_moves : nullptr;
   a.length = d_length;
   a.play = d_play;
   a.error = d_error;
-  HIPCHK(launch_ddave(a, (hipStream_t)stream));
+  HIPCHK(launch(a, (hipStream_t)stream));
   return PCGRL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Dangerous Dave levels
+// include/pcgrl_amd_ddave.h; kernels in ddave/pcgrl_ddave.h.  No handle, as for the Mario levels above.  The measures and the
+// diversity are the (7, 3, 512) instantiation of the wave body through the host path of "measures and diversity" above.
+extern "C" {
+
+int64_t pcgrl_ddave_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t solver_power) {
+  return pt_workspace_bytes("pcgrl_ddave_workspace_bytes", n, h, w, solver_power);
+}
+
+int pcgrl_ddave_evaluate(const pcgrl_ddave_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
+                         int64_t workspace_bytes, int32_t move_cap, int32_t *d_stats, int8_t *d_moves, int32_t *d_length,
+                         int32_t *d_play, uint32_t *d_error, void *stream) {
+  const char *who = "pcgrl_ddave_evaluate";
+  if (!cfg) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  return pt_evaluate(who, "pcgrl_ddave_workspace_bytes", launch_ddave, cfg->h, cfg->w, cfg->solver_power, n, d_grids,
+                     d_workspace, workspace_bytes, move_cap, d_stats, d_moves, d_length, d_play, d_error, stream);
 }
 
 int pcgrl_ddave_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
                                    double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
   const char *who = "pcgrl_ddave_measures_for_grids";
   int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = dd_check_shape(who, h, w);
+  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
   return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_dd_measures, d_counts, d_match, d_forms, d_entropy,
                           d_entropy_tab, stream);
@@ -2530,7 +2544,7 @@ int pcgrl_ddave_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8
                                     int32_t *d_pairwise, void *stream) {
   const char *who = "pcgrl_ddave_diversity_for_grids";
   int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = dd_check_shape(who, h, w);
+  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
   return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), DD_MEAS_PLANES, launch_dd_measures, group, d_scratch, d_sum,
                            d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
@@ -2542,60 +2556,19 @@ int pcgrl_ddave_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8
 // include/pcgrl_amd_mdungeon.h; kernels in mdungeon/pcgrl_mdungeon.h.  No handle, as for the Dangerous Dave levels above.  The
 // measures and the diversity are the (8, 3, 512) instantiation of the wave body through the host path of "measures and
 // diversity" above.
-static int md_check_shape(const char *who, int32_t h, int32_t w) {
-  if (h < 1 || h > MD_MAX_H || w < 1 || w > MD_MAX_W)
-    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..16 rows and 1..32 columns only");
-  return PCGRL_OK;
-}
-
-static int md_check_power(const char *who, int32_t power) {
-  if (power < 1 || power > MD_MAX_POWER)
-    return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": solver_power must be in [1, " + std::to_string(MD_MAX_POWER) + "]");
-  return PCGRL_OK;
-}
-
 extern "C" {
 
 int64_t pcgrl_mdungeon_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t solver_power) {
-  const char *who = "pcgrl_mdungeon_workspace_bytes";
-  if (n < 1) {
-    fail(PCGRL_EINVAL, std::string(who) + ": n must be at least 1");
-    return -1;
-  }
-  if (md_check_shape(who, h, w) != PCGRL_OK || md_check_power(who, solver_power) != PCGRL_OK) return -1;
-  return (int64_t)n * md_ws_stride(solver_power);
+  return pt_workspace_bytes("pcgrl_mdungeon_workspace_bytes", n, h, w, solver_power);
 }
 
 int pcgrl_mdungeon_evaluate(const pcgrl_mdungeon_config *cfg, int32_t n, const uint8_t *d_grids, void *d_workspace,
                             int64_t workspace_bytes, int32_t move_cap, int32_t *d_stats, int8_t *d_moves, int32_t *d_length,
                             int32_t *d_play, uint32_t *d_error, void *stream) {
   const char *who = "pcgrl_mdungeon_evaluate";
-  if (!cfg || !d_grids || !d_stats || n < 1) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
-  if (move_cap < 0) return fail(PCGRL_EINVAL, std::string(who) + ": move_cap must not be negative");
-  int rc = md_check_shape(who, cfg->h, cfg->w);
-  if (rc == PCGRL_OK) rc = md_check_power(who, cfg->solver_power);
-  if (rc != PCGRL_OK) return rc;
-  const int64_t stride = md_ws_stride(cfg->solver_power);
-  if (!d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < (int64_t)n * stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than "
-                                                 "pcgrl_mdungeon_workspace_bytes");
-  MdArgs a{};
-  a.h = cfg->h;
-  a.w = cfg->w;
-  a.power = cfg->solver_power;
-  a.n = n;
-  a.grids = d_grids;
-  a.ws = (uint8_t *)d_workspace;
-  a.ws_stride = stride;
-  a.hash_cap = md_hash_cap(cfg->solver_power);
-  a.cap = move_cap;
-  a.stats = d_stats;
-  a.moves = move_cap > 0 ? d_moves : nullptr;
-  a.length = d_length;
-  a.play = d_play;
-  a.error = d_error;
-  HIPCHK(launch_mdungeon(a, (hipStream_t)stream));
-  return PCGRL_OK;
+  if (!cfg) return fail(PCGRL_EINVAL, std::string(who) + ": bad arguments");
+  return pt_evaluate(who, "pcgrl_mdungeon_workspace_bytes", launch_mdungeon, cfg->h, cfg->w, cfg->solver_power, n, d_grids,
+                     d_workspace, workspace_bytes, move_cap, d_stats, d_moves, d_length, d_play, d_error, stream);
 }
 
 int pcgrl_mdungeon_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
@@ -2603,7 +2576,7 @@ int pcgrl_mdungeon_measures_for_grids(int32_t h, int32_t w, int32_t n, const uin
                                       void *stream) {
   const char *who = "pcgrl_mdungeon_measures_for_grids";
   int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = md_check_shape(who, h, w);
+  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
   return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_md_measures, d_counts, d_match, d_forms, d_entropy,
                           d_entropy_tab, stream);
@@ -2619,7 +2592,7 @@ int pcgrl_mdungeon_diversity_for_grids(int32_t h, int32_t w, int32_t n, const ui
                                        int32_t *d_pairwise, void *stream) {
   const char *who = "pcgrl_mdungeon_diversity_for_grids";
   int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = md_check_shape(who, h, w);
+  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
   if (rc != PCGRL_OK || n == 0) return rc;
   return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), MD_MEAS_PLANES, launch_md_measures, group, d_scratch, d_sum,
                            d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);

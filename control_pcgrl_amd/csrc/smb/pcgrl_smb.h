@@ -15,7 +15,8 @@
 //             LDS per wave, one wave per CU); the latency is hidden by occupancy instead -- 4.5 KB of LDS and one wave per
 //             level let a CU hold 32 levels.  The open list is CPython's heapq (heappush = append + _siftdown, heappop =
 //             move the last item to the root, _siftup to a leaf along the smaller children, _siftdown back), ordered by f
-//             alone with `<`, because the sift order decides which of several equal-f nodes is expanded first.  The loop body is
+//             alone with `<`, because the sift order decides which of several equal-f nodes is expanded first: pt_heap_push<17>
+//             and pt_heap_pop<17> of playthrough/pcgrl_playthrough.h, which the Dave and MiniDungeon solvers use at 16 bits.  The loop body is
 //             smb_search_iteration, the start smb_search_start and the finished search's tail smb_play_result: the budgeted,
 //             resumable search of smb/pcgrl_smb_ready.h runs the same three.
 //   memory    per level a workspace slot in HBM: nodes (8 B: x 8 | y+5 5 | airTime 3 | jumps 14 | action 2 ; parent 17 |
@@ -29,6 +30,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "../playthrough/pcgrl_playthrough.h"  // pt_heap_push, pt_heap_pop, pt_wave_sum
 
 namespace pcgrl {
 
@@ -113,60 +116,10 @@ __device__ __forceinline__ double smb_target_loss(const int32_t *has_trg, const 
   return loss;
 }
 
-__device__ __forceinline__ int smb_wave_sum(int v) {
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ bool smb_movable(const uint16_t *col, int H, int LW, int x, int y) {
   if (y < 0) return true;  // checkMovableLocation: above the level everything is free, whatever x
   if (x >= LW || y >= H) return false;
   return ((col[x] >> y) & 1u) == 0;
-}
-
-__device__ __forceinline__ uint32_t smb_key(uint32_t e) { return e >> 17; }
-
-// heapq.heappush: the item goes to the end, then _siftdown(heap, 0, n - 1)
-__device__ __forceinline__ void smb_heap_push(uint32_t *heap, int &n, uint32_t item) {
-  int pos = n++;
-  while (pos > 0) {
-    const int pp = (pos - 1) >> 1;
-    const uint32_t parent = heap[pp];
-    if (!(smb_key(item) < smb_key(parent))) break;
-    heap[pos] = parent;
-    pos = pp;
-  }
-  heap[pos] = item;
-}
-
-// heapq.heappop: the last item replaces the root, _siftup(heap, 0)
-__device__ __forceinline__ uint32_t smb_heap_pop(uint32_t *heap, int &n) {
-  const uint32_t last = heap[--n];
-  if (n == 0) return last;
-  const uint32_t ret = heap[0];
-  int pos = 0, child = 1;
-  while (child < n) {  // bubble the smaller child up until a leaf
-    uint32_t c = heap[child];
-    if (child + 1 < n) {
-      const uint32_t r = heap[child + 1];
-      if (!(smb_key(c) < smb_key(r))) {
-        c = r;
-        child++;
-      }
-    }
-    heap[pos] = c;
-    pos = child;
-    child = 2 * pos + 1;
-  }
-  while (pos > 0) {  // _siftdown(heap, 0, pos) of the item that was last
-    const int pp = (pos - 1) >> 1;
-    const uint32_t parent = heap[pp];
-    if (!(smb_key(last) < smb_key(parent))) break;
-    heap[pos] = parent;
-    pos = pp;
-  }
-  heap[pos] = last;
-  return ret;
 }
 
 __device__ __forceinline__ uint2 smb_pack(int x, int y, int air, int jumps, int action, uint32_t parent, int depth) {
@@ -200,7 +153,7 @@ __device__ __forceinline__ void smb_search_start(uint2 *nodes, uint32_t *heap, i
 __device__ __forceinline__ bool smb_search_iteration(const uint16_t *col, uint32_t *seen, uint2 *nodes, uint32_t *heap, int H,
                                                      int LW, int ex, int balance, int &nn, int &hn, uint32_t &best, int &best_x,
                                                      int &best_depth) {
-  const uint32_t cur = smb_heap_pop(heap, hn) & 0x1FFFFu;
+  const uint32_t cur = pt_heap_pop<17>(heap, hn) & 0x1FFFFu;
   const uint2 nd = nodes[cur];
   const int x = smb_nx(nd), y = smb_ny(nd), air = smb_nair(nd), jumps = smb_njumps(nd), depth = smb_ndepth(nd);
   if (y >= H) return false;  // a lose node
@@ -240,7 +193,7 @@ __device__ __forceinline__ bool smb_search_iteration(const uint16_t *col, uint32
       cy = y + 1;
     }
     nodes[nn] = smb_pack(cx, cy, cair, cj, a, cur, depth + 1);
-    smb_heap_push(heap, hn, ((uint32_t)((ex - cx) + balance * (depth + 1)) << 17) | (uint32_t)nn);
+    pt_heap_push<17>(heap, hn, ((uint32_t)((ex - cx) + balance * (depth + 1)) << 17) | (uint32_t)nn);
     nn++;
   }
   return false;
@@ -299,11 +252,11 @@ __device__ inline void smb_scan_level(SmbLds &L, int H, int W, SmbResult &r) {
     const int x = lane < 3 ? lane : W + lane;
     L.col[x] = (uint16_t)(border | (x == W + 4 ? 1u << (H - 3) : 0u));
   }
-  r.stats[0] = smb_wave_sum(dist_floor);
-  r.stats[1] = smb_wave_sum(tubes);
-  r.stats[2] = smb_wave_sum(enemies);
-  r.stats[3] = smb_wave_sum(empty);
-  r.stats[4] = smb_wave_sum(noise);
+  r.stats[0] = pt_wave_sum(dist_floor);
+  r.stats[1] = pt_wave_sum(tubes);
+  r.stats[2] = pt_wave_sum(enemies);
+  r.stats[3] = pt_wave_sum(empty);
+  r.stats[4] = pt_wave_sum(noise);
 }
 
 // What a finished play-through leaves: the chain of its final node `fin` gives r.stats[5..8] (jumps, jumps-dist, dist-win,

@@ -213,6 +213,11 @@ def test_header_units_symbols_and_config():
     assert "asm" not in src.replace("namespace", "")
     assert "meas_wave_map<DD_MEAS_TILES, DD_MEAS_PLANES, DD_MAX_CELLS>" in src
     assert "DD_MEAS_TILES = 7, DD_MEAS_PLANES = 3" in src and "DD_MAX_CELLS = DD_MAX_H * DD_MAX_W" in src
+    # the play-through's common parts are written once (playthrough/pcgrl_playthrough.h): one heappop among the four headers
+    shared = "playthrough/pcgrl_playthrough.h"
+    assert shared in _lib.HEADERS and os.path.exists(os.path.join(_lib.CSRC, shared))
+    heads = (shared, "ddave/pcgrl_ddave.h", "mdungeon/pcgrl_mdungeon.h", "smb/pcgrl_smb.h")
+    assert [h for h in heads if re.search(r"\w+_heap_pop\(", open(os.path.join(_lib.CSRC, h)).read())] == [shared]
     assert b"0.7.0" in L.pcgrl_version()
 
 

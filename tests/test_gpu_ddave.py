@@ -220,6 +220,17 @@ def test_unaligned_grid_pointers(h, w, power, n):
             assert np.array_equal(_np(ev.measures(g).counts), mn.counts(maps[:n], T)), off
 
 
+def test_a_dirty_workspace_gives_the_same_results():
+    """nodes and heap are written before they are read and the tags are cleared before each stage: a workspace of 0xFF bytes
+    changes nothing"""
+    maps, want = levels_and_rules(7, 11, 200, 256)
+    with DDaveEvaluator((7, 11), DEV, solver_power=200, max_levels=256) as ev:
+        ev._workspace.fill_(-1)
+        assert_same(ev.evaluate(maps, move_cap=CAP), want, "dirty")
+        ev._workspace.fill_(-1)
+        assert_same(ev.evaluate(maps[:65], move_cap=CAP), cut(want, 0, 65), "dirty, again")
+
+
 def test_tile_ids_above_6_read_as_solid_and_set_the_error_bit():
     maps, _ = levels_and_rules(7, 11, 200, 256)
     dirty = maps[:16].copy()

@@ -264,6 +264,11 @@ def test_header_units_symbols_and_config():
     # the open list's integer image: the bias and the 16-bit bound follow from the item limit
     assert "MD_F_BIAS = 2 * 4 * MD_MAX_ITEMS" in src and "MD_MAX_ITEMS = 64" in src
     assert 2 * (33 + 17 + 20) + 2 * 16000 + 2 * 4 * 64 < 1 << 16
+    # the play-through's common parts are written once (playthrough/pcgrl_playthrough.h): one heappop among the four headers
+    shared = "playthrough/pcgrl_playthrough.h"
+    assert shared in _lib.HEADERS and os.path.exists(os.path.join(_lib.CSRC, shared))
+    heads = (shared, "ddave/pcgrl_ddave.h", "mdungeon/pcgrl_mdungeon.h", "smb/pcgrl_smb.h")
+    assert [h for h in heads if re.search(r"\w+_heap_pop\(", open(os.path.join(_lib.CSRC, h)).read())] == [shared]
     assert b"0.7.0" in L.pcgrl_version()
 
 
