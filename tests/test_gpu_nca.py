@@ -1,7 +1,10 @@
 """The NCA level generator on the device (include/pcgrl_amd_nca.h) against its numpy twins
-(control_pcgrl_amd/nca.py): levels, n_step, frames and the error bits are equal bit for bit, on every map size at which the
-kernel takes another path (a block of 64, 128, 192 or 256 lanes with one cell per lane up to 256 cells, several passes above 256
-cells), on the recorded reference roll-outs, and in one chain with the evaluators."""
+(control_pcgrl_amd/nca.py): levels, n_step, frames and the error bits are equal bit for bit.  What runs: every tile count 2..8
+(CASES has 2, 3 and 8; GEOMETRY all seven); blocks of 64 lanes (1 to 64 cells), 128 (65, 77, 128), 192 (129, 130, 192) and 256
+(195, 256), and several passes of 256 lanes above 256 cells with a last pass of 1, 4 or 49 cells or a full one (260, 512, 513,
+561, 4096); the recorded reference roll-outs (T = 2, 3, 8) and, for every tile count, the float64 statement of the step
+(tests/nca_reference.py); the pick on exact logits (ties in the middle, in the denormal band, at 0 and at 1; the shortcut's
+edges); a non-finite logit after valid steps; another stream; and the chains with the evaluators and the archive."""
 import functools
 import glob
 import os
@@ -10,10 +13,14 @@ import numpy as np
 import pytest
 import torch
 
+import archive_rules as AR
+import ddave_rules as DR
 import measures_numpy as mn
+import nca_reference as nr
 import pcgrl_oracle as po
 from conftest import GOLDEN
-from control_pcgrl_amd import NcaGenerator, VecPcgrlEnv, generator_for, nca
+from nca_reference import genomes, seeds
+from control_pcgrl_amd import DDaveEvaluator, NcaGenerator, VecPcgrlEnv, archive, archive_for, generator_for, nca
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,22 +34,6 @@ CASES = [((1, 1), 2, 10, 3, 5, False), ((1, 9), 3, 2, 3, 5, True), ((9, 1), 8, 1
 
 def _np(t):
     return t.cpu().numpy()
-
-
-def genomes(rng, G, T, scale=1.0):
-    """random genomes of about the reference's orthogonal init's size: unit-norm rows, small biases"""
-    out = np.empty((G, nca.n_params(T)), np.float32)
-    for g in range(G):
-        w = nca.unpack_weights(out[g], T)
-        for m, fan in ((w.w1, 9 * T), (w.w2, 32), (w.w3, 32)):
-            m[...] = rng.normal(0, 1.0 / np.sqrt(fan), m.shape) * 2.0
-        for b in (w.b1, w.b2, w.b3):
-            b[...] = rng.normal(0, 0.1, b.shape)
-    return out * np.float32(scale)
-
-
-def seeds(rng, lead, shape, T):
-    return rng.integers(0, T, size=tuple(lead) + tuple(shape)).astype(np.uint8)
 
 
 def device_run(gen, weights, init, n_steps=None, frames=True, out=None):
@@ -258,3 +249,208 @@ def test_chain_generate_stats_measures():
         gen.check_errors()
         env.check_errors()
     env.close()
+
+
+# ---- every tile count, block size and last pass -------------------------------------------------------------------------------
+
+# map shape -> the tile counts run on it: every T at 7 x 11 (128 lanes, Dave's stock map) and 13 x 20 (a second pass of four
+# cells) and on one more shape; every shape with two tile counts, one of them with a padded w3t row (5, 6, 7)
+GEOMETRY = {(7, 9): (5, 2),                # 63 cells: 64 lanes
+            (5, 13): (6, 3),               # 65: 128 lanes
+            (7, 11): (2, 3, 4, 5, 6, 7, 8),  # 77: 128 lanes
+            (8, 16): (7, 4),               # 128: 128 lanes, full
+            (3, 43): (5, 8),               # 129: 192 lanes
+            (12, 16): (6, 2),              # 192: 192 lanes, full
+            (13, 15): (7, 3),              # 195: 256 lanes
+            (13, 20): (2, 3, 4, 5, 6, 7, 8),  # 260: a second pass of 4 cells
+            (8, 64): (5, 4),               # 512: two full passes
+            (19, 27): (6, 8)}              # 513: a third pass of one cell
+GEOMETRY_CASES = [(shape, T) for shape, tiles in GEOMETRY.items() for T in tiles]
+EXEMPT_CAP = 0.02  # as tests/test_nca_cpu.py
+
+
+@pytest.mark.parametrize("n", range(len(GEOMETRY_CASES)), ids=[f"{s[0]}x{s[1]}-T{T}" for s, T in GEOMETRY_CASES])
+def test_every_tile_count_and_block_size(n):
+    shape, T = GEOMETRY_CASES[n]
+    G, S, n_steps, per = 2, 3, 4, bool(n % 2)
+    rng = np.random.default_rng(3850 + n)
+    w = genomes(rng, G, T)
+    init = seeds(rng, (G, S) if per else (S,), shape, T)
+    want = nca.generated(w, init, n_steps, n_tiles=T)
+    with NcaGenerator(T, shape, n_steps=n_steps, device=DEV) as gen:
+        same(device_run(gen, w, init), want, (shape, T))
+        bare = device_run(gen, w, init, frames=False)
+        assert bare.frames is None
+        same(bare, want, (shape, T))
+        # the single steps of the twin's trajectory against the float64 statement of the step
+        first = np.broadcast_to(init, (G,) + init.shape[-3:])
+        prev = np.concatenate([first[:, :, None], want.frames[:, :, :-1]], axis=2)  # the map before step k
+        idx = np.argwhere(np.arange(n_steps)[None, None, :] <= want.n_step[:, :, None])
+        maps = prev[idx[:, 0], idx[:, 1], idx[:, 2]]
+        one = device_run(gen, w[idx[:, 0]], maps[:, None], n_steps=1, frames=False)
+        got = _np(one.levels)[:, 0]
+        l64 = np.stack([nr.logits64(w[g], m, T) for g, m in zip(idx[:, 0], maps)])
+        ex = nr.exempt(l64)
+        print(f"{shape} T = {T}: exempt share {ex.mean():.5f} of {ex.size} cells")
+        assert ex.mean() <= EXEMPT_CAP and not (got != np.argmax(l64, axis=-3))[~ex].any()
+        assert np.array_equal(got, want.frames[idx[:, 0], idx[:, 1], idx[:, 2]])
+        assert gen.poll_errors() == want.error_bits == 0
+
+
+# ---- the pick on exact logits -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("T", range(2, 9))
+def test_pick_on_exact_logits(T):
+    """a genome that is zero but for l3.bias has exactly that vector as every cell's logits (a -0.0 becomes +0.0 when the
+    zero products are added): one genome on a 1 x 1 map is one probe of the pick, the whole probe set one launch"""
+    p = nr.probe_vectors(T, np.random.default_rng(380 + T))
+    w = nr.bias_genomes(p.vectors, T)
+    assert len(w) <= (3000 if T <= 4 else 2000) and w.nbytes < 30e6
+    init = np.zeros((1, 1, 1), np.uint8)
+    for g in range(0, len(w), 97):
+        _, logits = nca.stepped(w[g], init[0], n_tiles=T)
+        assert np.array_equal(logits[:, 0, 0], p.vectors[g])
+    twin = np.argmax(nca.sigmoid32(p.vectors), axis=-1)
+    ref, gap = nr.pick_ref(p.vectors)
+    keep = gap >= nr.GAP_FLOOR
+    with NcaGenerator(T, (1, 1), n_steps=1, device=DEV) as gen:
+        out = device_run(gen, w, init, frames=False)
+        got = _np(out.levels)[:, 0, 0, 0]
+        bad = np.flatnonzero(got != twin)
+        assert bad.size == 0, [(int(i), str(p.family[i]), p.vectors[i].tolist(), int(got[i]), int(twin[i])) for i in bad[:8]]
+        assert (~keep).sum() <= 0.001 * len(keep) and np.array_equal(got[keep], ref[keep])
+        assert (_np(out.n_step) == 0).all()
+        assert gen.poll_errors() == 0
+
+
+# ---- a non-finite logit after valid steps -------------------------------------------------------------------------------------
+
+def overflow_genome(T=4):
+    """Reads centre taps only.  A cell of tile 1 becomes 2 (unit 3 carries 2 to logit 2), a cell of tile 2 becomes 3 (unit 4),
+    a cell of tile 0 stays (all logits equal: the first index).  At a cell of tile 3 units 0 and 1 are 3e38 each and layer 2
+    adds them: inf, and 0 * inf in layer 3 -- a NaN in every logit of that one cell."""
+    g = np.zeros(nca.n_params(T), np.float32)
+    w = nca.unpack_weights(g, T)
+    w.w1[3, 1, 1, 1] = w.w2[3, 3] = w.w1[4, 2, 1, 1] = w.w2[4, 4] = 1.0
+    w.w3[2, 3] = w.w3[3, 4] = 2.0
+    w.w1[0, 3, 1, 1] = w.w1[1, 3, 1, 1] = 3e38
+    w.w2[0, 0] = w.w2[0, 1] = 1.0
+    return g
+
+
+def first_nonfinite(w, init, T, n_steps):
+    """the twin's first step with a non-finite logit on one map, or None"""
+    cur = init
+    for step in range(n_steps):
+        nxt, logits = nca.stepped(w, cur, n_tiles=T)
+        if not np.isfinite(logits).all():
+            return step
+        if (nxt == cur).all():
+            return None
+        cur = nxt
+    return None
+
+
+@pytest.mark.parametrize("shape", [(16, 16), (17, 33)], ids=["16x16", "17x33"])
+def test_nonfinite_after_the_first_step(shape):
+    """the refusal overwrites the frame rows that valid steps wrote, also where a lane owns several cells (17 x 33: three
+    passes; the cell that overflows is in the last pass, in the second, or is cell 0)"""
+    T, n_steps, rng = 4, 6, np.random.default_rng(3860)
+    H, W = shape
+    w = genomes(rng, 3, T)
+    w[1] = overflow_genome(T)
+    init = seeds(rng, (3, 4), shape, T)
+    init[1] = 0
+    init[1, 0, H - 1, W - 1] = 1   # 1 -> 2 -> 3 -> overflow at step 2, in the last cell
+    init[1, 1, H // 2, 3] = 2      # 2 -> 3 -> overflow at step 1, mid-map
+    init[1, 2, 0, 0] = 2           # the same in cell 0, with a tile 1 that is still on its way
+    init[1, 2, H - 1, 0] = 1
+    assert first_nonfinite(w[1], init[1, 0], T, n_steps) == 2 and first_nonfinite(w[1], init[1, 1], T, n_steps) == 1
+    assert first_nonfinite(w[1], init[1, 2], T, n_steps) == 1 and first_nonfinite(w[1], init[1, 3], T, n_steps) is None
+    want = nca.generated(w, init, n_steps, n_tiles=T)
+    assert want.error_bits == nca.ERR_NONFINITE and want.n_step[1].tolist() == [-1, -1, -1, 0]
+    assert (want.n_step[[0, 2]] >= 0).all() and (want.frames[1, :3] == init[1, :3, None]).all()
+    with NcaGenerator(T, shape, n_steps=n_steps, device=DEV) as gen:
+        out = device_run(gen, w, init)
+        same(out, want, shape)
+        assert np.array_equal(_np(out.levels)[1], init[1]) and (_np(out.frames)[1] == init[1][:, None]).all()
+        assert gen.poll_errors() == nca.ERR_NONFINITE and gen.poll_errors() == 0
+        same(device_run(gen, w, init, frames=False), want, shape)
+        assert gen.poll_errors() == nca.ERR_NONFINITE and gen.poll_errors() == 0
+
+
+# ---- with the Dave evaluator and the archive; another stream ------------------------------------------------------------------
+
+def test_generation_with_the_dave_evaluator():
+    """generate -> evaluate -> behaviour -> archive add -> ask on one stream with no host sync in between: T = 7 on Dave's
+    7 x 11 map (128 lanes), against the twin's maps through tests/ddave_rules.py, the numpy measures and
+    tests/archive_rules.py"""
+    rng = np.random.default_rng(3870)
+    G, S, T, names = 6, 4, 7, ["emptiness", "symmetry"]
+    ev = DDaveEvaluator((7, 11), DEV, solver_power=200, max_levels=64)
+    gen, arc = generator_for(ev), archive_for(ev, names, bins=10)
+    assert (gen.n_tiles, gen.map_shape, gen.n_params) == (T, (7, 11), nca.n_params(T))
+    w, init = genomes(rng, G, T), seeds(rng, (S,), (7, 11), T)
+    out = device_run(gen, w, init, frames=False)
+    levels = out.levels.reshape(G * S, 7, 11)
+    res = ev.evaluate(levels)
+    objective = ev.reward(res["stats"], torch.zeros_like(res["stats"]))
+    beh = ev.behaviour(levels, names)
+    added = arc.add(levels, objective, beh)
+    kids, parent = arc.ask(16, seed=5, rate=0.05)
+    # everything above is enqueued; from here on the host reads
+    want = nca.generated(w, init, 10, n_tiles=T)
+    same(out, want)
+    maps = want.levels.reshape(G * S, 7, 11)
+    assert len(np.unique(maps.reshape(G * S, -1), axis=0)) > 1
+    rows = [DR.outputs(m, 200, 0) for m in maps]
+    stats = np.asarray([r[0] for r in rows], np.int32)
+    assert np.array_equal(_np(res["stats"]), stats)
+    assert np.array_equal(_np(res["play"]), np.asarray([r[3] for r in rows], np.int32))
+    want_obj = np.array([DR.reward(s, [0] * 11) for s in stats], np.float64)
+    assert np.array_equal(_np(objective).view(np.uint64), want_obj.view(np.uint64))
+    bc = mn.bc_from_integers(mn.counts(maps, T), mn.matches(maps, T), 7, 11, T)
+    want_beh = np.stack([bc[k] for k in names], 1)
+    assert np.array_equal(_np(beh).view(np.uint64), want_beh.view(np.uint64))
+    ref = AR.SeqArchive(arc.dims, arc.bounds, (7, 11))
+    status, cell, counts = ref.add(maps, want_obj, want_beh)
+    assert np.array_equal(_np(added.status), status) and np.array_equal(_np(added.cell), cell)
+    assert np.array_equal(_np(added.counts), counts) and counts[0] >= 1 and counts[2] == 0
+    d = arc.dense()
+    assert np.array_equal(_np(d.occupied), ref.flag) and np.array_equal(_np(d.grids), ref.maps)
+    assert np.array_equal(_np(d.objectives).view(np.uint64), ref.obj.view(np.uint64))
+    occ = ref.occupied()
+    pc = occ[archive.sampled_parents(5, 0, 16, len(occ))]
+    assert np.array_equal(_np(parent), pc) and np.array_equal(_np(kids), archive.mutated(ref.maps[pc], 5, 0, 0.05, T))
+    gen.check_errors(), ev.check_errors(), arc.check_errors()
+    gen.close(), arc.close(), ev.close()
+    # and generator_for on an env with five tiles
+    env = VecPcgrlEnv("sokoban", "narrow", (8, 8), 1, device=DEV)
+    with generator_for(env, n_steps=5) as gen:
+        assert (gen.n_tiles, gen.map_shape, gen.n_steps) == (5, (8, 8), 5)
+        w, init = genomes(rng, 3, 5), seeds(rng, (3, 2), (8, 8), 5)
+        same(device_run(gen, w, init), nca.generated(w, init, 5, n_tiles=5))
+        gen.check_errors()
+    env.close()
+
+
+def test_side_stream_and_second_run_are_byte_identical():
+    rng = np.random.default_rng(3880)
+    T, shape, G, S = 6, (7, 11), 4, 3
+    with NcaGenerator(T, shape, n_steps=8, device=DEV) as gen:
+        w = torch.as_tensor(genomes(rng, G, T)).to(DEV)
+        init = torch.as_tensor(seeds(rng, (G, S), shape, T)).to(DEV)
+        first = gen.generate(w, init, frames=True)
+        second = gen.generate(w, init, frames=True)
+        side = torch.cuda.Stream(DEV)
+        side.wait_stream(torch.cuda.current_stream(DEV))
+        with torch.cuda.stream(side):
+            third = gen.generate(w, init, frames=True)
+            assert gen.poll_errors() == 0  # (synchronises the side stream)
+        torch.cuda.current_stream(DEV).wait_stream(side)
+        for other in (second, third):
+            for name in ("levels", "n_step", "frames"):
+                assert getattr(other, name).data_ptr() != getattr(first, name).data_ptr()
+                assert torch.equal(getattr(other, name), getattr(first, name)), name
+        same(first, nca.generated(_np(w), _np(init), 8, n_tiles=T))
+        assert gen.poll_errors() == 0

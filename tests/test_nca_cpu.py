@@ -1,12 +1,14 @@
 """The numpy twins of the NCA level generator (control_pcgrl_amd/nca.py; include/pcgrl_amd_nca.h) against
 the roll-outs recorded from the reference's NCA class (tools/gen_golden_nca.py -> tests/golden/nca), the stated properties of
-sigmoid32, the genome layout and the refusals.  No GPU."""
+sigmoid32, the genome layout and the refusals; for every tile count against the float64 statement of the step and the correctly
+rounded sigmoid of tests/nca_reference.py, on random genomes and on the probe set the device's pick is held to.  No GPU."""
 import glob
 import os
 
 import numpy as np
 import pytest
 
+import nca_reference as nr
 from conftest import GOLDEN
 from control_pcgrl_amd import NcaGenerator, generator_for, nca
 
@@ -171,6 +173,102 @@ def test_channels_the_kernel_skips_cannot_tie():
     skipped = ((lmax - l) > np.float32(1.0)) & (lmax > np.float32(-87.0))
     assert skipped.sum() > 300_000 and ((lmax - l)[skipped] < np.float32(1.001)).all()
     assert (nca.sigmoid32(lmax[skipped]) > nca.sigmoid32(l[skipped])).all()
+
+
+@pytest.mark.parametrize("T", range(2, 9))
+def test_twin_equals_the_float64_reference(T):
+    """random genomes, six steps of five seeds at 9 x 13 and 16 x 16 along the twin's own trajectory: on every cell that the
+    recorder's rule does not exempt, the twin's pick is the float64 argmax.  (The float32 logits stay within 1e-5 of the float64
+    ones, a hundredth of the exemption's margin; measured 2.3e-6.)"""
+    rng = np.random.default_rng(3800 + T)
+    cells = exempted = wrong = 0
+    err = 0.0
+    for shape in ((9, 13), (16, 16)):
+        for w in nr.genomes(rng, 2, T):
+            cur = nr.seeds(rng, (5,), shape, T)
+            for _ in range(6):
+                nxt, l32 = nca.stepped(w, cur, n_tiles=T)
+                l64 = nr.logits64(w, cur, T)
+                ex = nr.exempt(l64)
+                cells += ex.size
+                exempted += int(ex.sum())
+                wrong += int((nxt != np.argmax(l64, axis=-3))[~ex].sum())
+                err = max(err, float(np.abs(l64 - l32).max()))
+                cur = nxt
+    print(f"T = {T}: exempt share {exempted / cells:.5f} of {cells} cells, {wrong} disagree, max |float64 - float32 logit| {err:.2e}")
+    assert wrong == 0 and exempted / cells <= EXEMPT_CAP and err < 1e-5
+
+
+def _probes(T):
+    return nr.probe_vectors(T, np.random.default_rng(380 + T))
+
+
+def test_sigmoid32_is_the_correctly_rounded_sigmoid():
+    x = np.unique(np.concatenate([_probes(T).vectors.ravel() for T in range(2, 9)]).view(np.uint32)).view(np.float32)
+    want, gap = nr.sigmoid_cr32(x)
+    keep = gap >= nr.GAP_FLOOR
+    differ = int((nca.sigmoid32(x)[keep].view(np.uint32) != want[keep].view(np.uint32)).sum())
+    print(f"{len(x)} scalars, {int((~keep).sum())} excluded, {differ} differ, smallest gap {gap.min():.2e}")
+    assert len(x) > 10_000 and (~keep).sum() <= 0.001 * len(x)
+    assert differ == 0
+
+
+@pytest.mark.parametrize("T", range(2, 9))
+def test_probe_set_discriminates(T):
+    """the probe set of test_gpu_nca.test_pick_on_exact_logits, from the twin alone: it holds ties and non-ties where a wrong
+    pick would show, both branches of the kernel's shortcut at each threshold, and vectors on which the shortcut without its
+    `lmax > -87` answers wrongly"""
+    p = _probes(T)
+    v, n = p.vectors, np.arange(len(p.vectors))
+    assert 1000 <= len(v) <= 3000 and len(np.unique(v.view(np.uint32), axis=0)) > 0.95 * len(v)
+    s = nca.sigmoid32(v)
+    twin = np.argmax(s, axis=-1)
+    pair = p.lo >= 0
+    lo, hi = v[n, p.lo], v[n, p.hi]
+    assert (lo[pair] <= hi[pair]).all() and (p.lo[pair] < p.hi[pair]).all()
+    tie = s[n, p.lo] == s[n, p.hi]
+    adj = p.family == "adjacent"
+    band = adj & (hi > -104) & (hi < -87)
+    print(f"T = {T}: {len(v)} probes; adjacent floats: {int(tie[adj].sum())} ties, {int((~tie)[adj].sum())} non-ties of "
+          f"{int(adj.sum())}; in the denormal band {int(tie[band].sum())} and {int((~tie)[band].sum())}")
+    assert tie[adj].sum() >= adj.sum() / 4 and (~tie)[adj].sum() >= adj.sum() / 4
+    assert tie[band].any() and (~tie)[band].any()
+    if T == 2:
+        assert np.array_equal(twin[adj] == 0, tie[adj])  # the lower index is the answer exactly when the sigmoids tie
+    for fam in ("zero", "plateau", "zeros"):
+        assert tie[p.family == fam].all()
+    wide = (p.family == "denormal") & (hi - lo > np.float32(1.0))
+    assert tie[wide].any() and (~tie)[wide].any()
+    # the shortcut's branches, in float32 as the kernel computes them
+    cannot_tie = ((hi - lo) > np.float32(1.0)) & (lo < np.float32(12.0)) & (hi > np.float32(-87.0))
+    for e, (below, above) in enumerate((((hi - lo) <= np.float32(1.0), (hi - lo) > np.float32(1.0)),
+                                        (lo >= np.float32(12.0), lo < np.float32(12.0)),
+                                        (hi <= np.float32(-87.0), hi > np.float32(-87.0)))):
+        at = p.edge == e
+        taken = {True: int((cannot_tie & at).sum()), False: int((~cannot_tie & at).sum())}
+        print(f"  threshold {e}: {taken[True]} probes skip the rival, {taken[False]} evaluate it")
+        assert taken[True] >= 3 and taken[False] >= 3 and (below & at).any() and (above & at).any()
+        if e == 0:
+            assert ((hi - lo) == np.float32(1.0))[at].any()
+    assert ((lo == np.nextafter(np.float32(12.0), np.float32(0)))[p.edge == 1]).any() and (lo == np.float32(12.0))[p.edge == 1].any()
+    assert ((hi == np.nextafter(np.float32(-87.0), np.float32(0)))[p.edge == 2]).any() and (hi == np.float32(-87.0))[p.edge == 2].any()
+    # the kernel's organisation of the pick gives the twin's answer; without the guard on lmax it does not
+    pick, skipped = nr.kernel_pick(v)
+    assert np.array_equal(pick, twin) and skipped.any()
+    assert np.array_equal(skipped[n, np.maximum(p.lo, 0)][p.edge >= 0], cannot_tie[p.edge >= 0] & (lo < hi)[p.edge >= 0])
+    unguarded, _ = nr.kernel_pick(v, lmax_guard=False)
+    assert (unguarded != twin).sum() >= 50
+    if T > 2:
+        sev = p.family == "several"
+        j = np.argmax(v, axis=-1)
+        assert (twin[sev] < j[sev]).sum() >= 20 and (twin[sev] == j[sev]).sum() >= 20  # ties that win, near-misses that do not
+        assert (skipped[sev].sum(axis=-1) >= 1).sum() >= 20
+        assert ((v[sev] == v[sev][:, :1]).all(axis=-1)).sum() >= 6  # all T equal
+    # the correctly rounded sigmoid picks the same
+    ref, gap = nr.pick_ref(v)
+    keep = gap >= nr.GAP_FLOOR
+    print(f"  {int((~keep).sum())} probes excluded")
+    assert (~keep).sum() <= 0.001 * len(v) and np.array_equal(ref[keep], twin[keep])
 
 
 def test_the_unit_is_listed():
