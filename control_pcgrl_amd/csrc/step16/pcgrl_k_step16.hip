@@ -246,6 +246,117 @@ __device__ inline void binary_stats_update16(const Grp<16> &g, uint32_t x, uint3
   }
 }
 
+// ---- the observe wave's encoder (development switches: A/B builds)
+#ifndef PCGRL_STEP16_OBS_FIRST
+#define PCGRL_STEP16_OBS_FIRST 1  // 0: encode_obs_any, the observe role as it was before encode_obs16
+#endif
+#ifndef PCGRL_STEP16_OBS_PRIO
+#define PCGRL_STEP16_OBS_PRIO 0  // 1: the observe wave at the simulate wave's issue priority up to its last observation store
+#endif
+
+// store_obs16 / store_obs16_nt with the chunk's distance from `dst` in the instruction's offset field (one address per lane
+// for all chunks of a phase: a lane's chunks lie 256 bytes apart, twelve of them inside the field's 4 KB)
+template <bool NT, int OFF>
+__device__ __attribute__((always_inline)) inline void store_obs16_at(uint8_t *dst, const u32x4_t &w) {
+  static_assert(OFF >= 0 && OFF < 4096, "the offset field of a global store");
+  if constexpr (NT)
+    asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1 nt\n\ts_nop 1" : : "v"(dst), "v"(w), "n"(OFF) : "memory");
+  else
+    asm volatile("global_store_dwordx4 %0, %1, off offset:%2 " PCGRL_OBS_STORE_MODS "\n\ts_nop 1" : : "v"(dst), "v"(w), "n"(OFF) : "memory");
+}
+
+// Phase 1, chunk k = 16 * IT + row: stored when it lies in a border row, i.e. outside the 96 chunks from `lo` on
+// (r = row - lo; one unsigned compare).  A trip whose mask is empty in the whole wave is skipped by the branch on exec.
+template <bool NT, int IT>
+__device__ __attribute__((always_inline)) inline void obs16_border_chunk(uint8_t *dst, int r, const u32x4_t *pat) {
+  if ((unsigned)(r + 16 * IT) >= 96u) store_obs16_at<NT, 256 * IT>(dst, pat[IT % 3]);
+}
+template <bool NT>
+__device__ __attribute__((always_inline)) inline void obs16_border(uint8_t *dst, int r, const u32x4_t *pat) {
+  obs16_border_chunk<NT, 0>(dst, r, pat);
+  obs16_border_chunk<NT, 1>(dst, r, pat);
+  obs16_border_chunk<NT, 2>(dst, r, pat);
+  obs16_border_chunk<NT, 3>(dst, r, pat);
+  obs16_border_chunk<NT, 4>(dst, r, pat);
+  obs16_border_chunk<NT, 5>(dst, r, pat);
+  obs16_border_chunk<NT, 6>(dst, r, pat);
+  obs16_border_chunk<NT, 7>(dst, r, pat);
+  obs16_border_chunk<NT, 8>(dst, r, pat);
+  obs16_border_chunk<NT, 9>(dst, r, pat);
+  obs16_border_chunk<NT, 10>(dst, r, pat);
+  obs16_border_chunk<NT, 11>(dst, r, pat);
+}
+template <bool NT>
+__device__ __attribute__((always_inline)) inline void obs16_map_rows(uint8_t *dst, const uint4 *v) {
+  store_obs16_at<NT, 0>(dst, u32x4_t{v[0].x, v[0].y, v[0].z, v[0].w});
+  store_obs16_at<NT, 256>(dst, u32x4_t{v[1].x, v[1].y, v[1].z, v[1].w});
+  store_obs16_at<NT, 512>(dst, u32x4_t{v[2].x, v[2].y, v[2].z, v[2].w});
+  store_obs16_at<NT, 768>(dst, u32x4_t{v[3].x, v[3].y, v[3].z, v[3].w});
+  store_obs16_at<NT, 1024>(dst, u32x4_t{v[4].x, v[4].y, v[4].z, v[4].w});
+  store_obs16_at<NT, 1280>(dst, u32x4_t{v[5].x, v[5].y, v[5].z, v[5].w});
+}
+
+// encode_obs<PCGRL_PROB_BINARY, 16, /*FAST=*/true, uint32_t> (pcgrl_kernels2d.h) for this kernel: the same bytes -- the 32x32
+// window around pos over the 16x16 map, one-hot with C = 3 channels, channel-last: 32 rows of six 16-byte chunks, chunk k of
+// the env at byte 16 k -- in another order.  The map fills observation rows [16 - pos0, 32 - pos0): chunks [lo, lo + 96) with
+// lo = 6 * (16 - pos0).  The other 96 chunks show nothing but "outside the map" (byte j of a row is 1 iff j % 3 == 0).
+//
+// Phase 1: the border chunks, from registers, before any LDS traffic.  Lane `row` owns chunks k = 16 it + row, it = 0..11;
+// the pattern of chunk k starts at phase (16 k) % 3 = k % 3 = (it + row) % 3 of the dword sequence A B C A B C ..., so
+// the lane keeps three dwords (the sequence from row % 3 on) as three quads and trip `it` stores quad it % 3.
+// Phase 2: every lane builds the 96 bytes of its own map row in LDS as encode_obs does (the out-of-bounds pattern, then
+// one byte pair per cell, the wave's four envs starting four cells apart: see there), and the group streams the 96
+// map-row chunks: lane `row` takes the six k == row (mod 16) of [lo, lo + 96), i.e. t = d + 16 j with d = (row - lo) & 15 =
+// (row + 6 pos0) & 15.  Chunk t of the map rows is chunk t % 6 of map row t / 6 and lies 16 (t + t / 6) bytes into the
+// env's LDS rows (stride 112); with d = 6 m0 + q0, floor((q0 + 16 j) / 6) - floor(16 j / 6) is [q0 >= 2] for j = 1, 4,
+// [q0 >= 4] for j = 2, 5 and 0 for j = 0, 3: three addresses per lane and six constant offsets, no division per chunk.
+// (No row of LDS for the shared out-of-bounds row any more; the host still passes the same LDS size.)
+__device__ inline void encode_obs16(const Grp<16> &g, const Params &p, int env, bool active, const uint32_t *b, const int *pos,
+                                    uint8_t *lds) {
+  constexpr int C = 3, FCH = 6, STRIDE = FCH * 16 + 16, ENV_BYTES = 32 * 32 * C;
+  const bool nt = (p.obs16 & 2) != 0;  // (wave-uniform: scalar branches)
+  uint8_t *base = p.obs + (size_t)env * ENV_BYTES;
+  const int lo = 6 * (16 - pos[0]);
+  if (active) {
+    constexpr uint32_t SEQ0 = 0x01000001u, SEQ1 = 0x00010000u, SEQ2 = 0x00000100u;  // bytes 0-3, 4-7, 8-11 of the pattern
+    const int r3 = g.row % 3;
+    const uint32_t x0 = r3 == 0 ? SEQ0 : r3 == 1 ? SEQ1 : SEQ2;
+    const uint32_t x1 = r3 == 0 ? SEQ1 : r3 == 1 ? SEQ2 : SEQ0;
+    const uint32_t x2 = r3 == 0 ? SEQ2 : r3 == 1 ? SEQ0 : SEQ1;
+    const u32x4_t pat[3] = {{x0, x1, x2, x0}, {x1, x2, x0, x1}, {x2, x0, x1, x2}};
+    uint8_t *dst = base + g.row * 16;
+    if (nt)
+      obs16_border<true>(dst, g.row - lo, pat);
+    else
+      obs16_border<false>(dst, g.row - lo, pat);
+  }
+  uint8_t *row = lds + g.lane * STRIDE;
+#pragma unroll
+  for (int q = 0; q < FCH; q++) *(uint4 *)(row + q * 16) = oob_chunk<C>(q % C);
+  const int left = pos[1] - 16;  // map column shown by obs column 0
+  const int rot = PCGRL_OBS_ROT ? 4 * (g.lane >> 4) : 0;
+#pragma unroll
+  for (int x = 0; x < 16; x++) {
+    const int xx = (x + rot) & 15;
+    const int o = (xx - left) * C;  // always inside the window
+    row[o] = 0;
+    row[o + 1 + tile_at<1, uint32_t>(b, xx)] = 1;
+  }
+  if (active) {
+    const int d = (g.row + 6 * pos[0]) & 15;
+    const int m0 = (d >= 6 ? 1 : 0) + (d >= 12 ? 1 : 0), q0 = d - 6 * m0;
+    const uint8_t *s0 = lds + g.gbase * STRIDE + 16 * (d + m0);
+    const uint8_t *s1 = s0 + (q0 >= 2 ? 16 : 0), *s2 = s0 + (q0 >= 4 ? 16 : 0);
+    const uint4 v[6] = {*(const uint4 *)s0,         *(const uint4 *)(s1 + 288),  *(const uint4 *)(s2 + 592),
+                        *(const uint4 *)(s0 + 896), *(const uint4 *)(s1 + 1184), *(const uint4 *)(s2 + 1488)};
+    uint8_t *dst = base + 16 * (lo + d);
+    if (nt)
+      obs16_map_rows<true>(dst, v);
+    else
+      obs16_map_rows<false>(dst, v);
+  }
+}
+
 // One workgroup = STEP16_PAIRS x (simulate wave, observe wave) over four envs each, as in step_kernel.  The role is decided
 // first; each role asks for all it needs of the old state in one batch and then meets the other at the barrier (the simulate
 // wave overwrites that state at its end).
@@ -270,6 +381,9 @@ __global__ __launch_bounds__(128 * STEP16_PAIRS, PCGRL_STEP_WAVES) void step16_k
 
   if (observer) {
     // ---- observe: the tile plane, pos / n_step, iteration / changes, the action; the RNG streams when a reset may come
+#if PCGRL_STEP16_OBS_PRIO
+    if (p.n_envs <= 8192) __builtin_amdgcn_s_setprio(3);  // (where the simulate wave raises its own, below)
+#endif
     TRACE_DECL();
     M b[1];
     b[0] = active ? pl[0] : M(0);
@@ -294,13 +408,21 @@ __global__ __launch_bounds__(128 * STEP16_PAIRS, PCGRL_STEP_WAVES) void step16_k
       obs_rp.load(rng_stash + 4);
       reset_from_rng<PROB, LPE, M>(g, p, e, do_reset, b, pos, /*commit=*/false, nullptr, &obs_rp, &obs_rr);
     }
+#if PCGRL_STEP16_OBS_FIRST
+    encode_obs16(g, p, e, active, b, pos, lds);
+#else
     encode_obs_any<PROB, LPE, true, M>(g, p, e, active, b, pos, lds);
+#endif
+#if PCGRL_STEP16_OBS_PRIO
+    if (p.n_envs <= 8192) __builtin_amdgcn_s_setprio(0);  // (the flood yields to the simulate waves again)
+#endif
+    [[maybe_unused]] const unsigned long long _tr_issued = TRACE_NOW();  // (behind the last observation store, before the flood)
     // PREFLOOD: the component of the next edit's cell, flooded ahead of time for the next launch's simulate wave
     const M xbit = (active && g.row == pos[0]) ? (M(1) << pos[1]) : M(0);
     const M comp = flood(g, xbit, (~b[0] & colmask) | xbit);
     if (active) pl[16 * PRE_PLANE] = comp | (M)PRE_VALID;
     TRACE_PUT(2, _tr0);
-    TRACE_PUT(3, TRACE_NOW());
+    TRACE_PUT(3, _tr_issued);
     TRACE_DRAIN();
     TRACE_PUT(4, TRACE_NOW());
     return;

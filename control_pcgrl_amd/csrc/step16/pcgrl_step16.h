@@ -6,7 +6,9 @@
 //     flags / last_loss / ep_return / stats[] behind it: a second dependent memory round trip on every simulate wave),
 //   * path sweeps that run every trip without the per-level bookkeeping and derive length, last level and visited set from
 //     the frontiers of the group's last live trip (sweep16),
-//   * the env record read and written back with 16-byte accesses.
+//   * the env record read and written back with 16-byte accesses,
+//   * an observation encoder of its own (encode_obs16): the chunks of the rows outside the map stored from registers first,
+//     the map rows through LDS behind them.
 // The host routes a step launch here when step16_applies() holds; every other launch takes launch_binary32 as before.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -97,6 +97,23 @@ for key in ("sim_start", "obs_start", "sim_end", "obs_issued", "obs_acked"):
     print(f"{key:11s} median wave {med:7.0f}   p95 {p95:7.0f}   last wave {mx:7.0f}")
 last = np.median([max(r["sim_end"].max(), r["obs_acked"].max()) * 10.0 for r in rows])
 print(f"last stamp of the launch {last:.0f} ns; per-launch time by HIP events (8 back-to-back) {np.median([r['per_launch_us'] for r in rows]):.2f} us")
+# which role ends the launch: the last simulate wave's end against the last observe wave's acknowledged stores, per launch
+sim_last = np.array([r["sim_end"].max() for r in rows]) * 10.0
+obs_last = np.array([r["obs_acked"].max() for r in rows]) * 10.0
+share = dict(observe=float(np.mean(obs_last > sim_last)), simulate=float(np.mean(sim_last > obs_last)), tie=float(np.mean(sim_last == obs_last)))
+print(f"the launch is ended by: an observe wave in {share['observe']:.1%} of the launches, a simulate wave in {share['simulate']:.1%}, "
+      f"both on one 10 ns tick in {share['tie']:.1%}; last observe ack - last simulate end: median {np.median(obs_last - sim_last):.0f} ns")
+dump = next((a[7:] for a in sys.argv if a.startswith("--json=")), None)
+if dump:
+    import json
+    rec = {key: dict(median_wave=float(np.median([q(r[key], 0.5) for r in rows])), p95=float(np.median([q(r[key], 0.95) for r in rows])),
+                     last_wave=float(np.median([q(r[key], 1.0) for r in rows])))
+           for key in ("sim_start", "obs_start", "sim_end", "obs_issued", "obs_acked")}
+    rec.update(unit="ns from the launch's first wave start; median over the traced launches", launches=len(rows), envs=n,
+               wave_pairs_per_workgroup=1, ended_by=share, obs_ack_minus_sim_end_median=float(np.median(obs_last - sim_last)),
+               last_stamp=float(last), per_launch_us_hip_events=float(np.median([r["per_launch_us"] for r in rows])))
+    with open(dump, "w") as f:
+        json.dump(rec, f, indent=1)
 simlife = np.median([np.mean(r["sim_end"] - r["sim_start"]) * 10.0 for r in rows])
 simmax = np.median([np.max(r["sim_end"] - r["sim_start"]) * 10.0 for r in rows])
 obslife = np.median([np.mean(r["obs_acked"] - r["obs_start"]) * 10.0 for r in rows])
