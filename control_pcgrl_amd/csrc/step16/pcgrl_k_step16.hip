@@ -2,7 +2,8 @@
 //
 // The same work as step_kernel<PCGRL_PROB_BINARY, 16, uint32_t, /*FAST=*/true, /*CTRL=*/false, 2> (pcgrl_kernels2d.h), bit for
 // bit, on the same state layout and with the same launch geometry; see pcgrl_step16.h for what differs.  Everything that is
-// not named *16 here is pcgrl_kernels2d.h's.
+// not named *16 here is pcgrl_kernels2d.h's.  The observe wave's encoder comes in two forms chosen by the batch size
+// (encode_obs16_regs up to 8 192 envs, encode_obs16 above); -DPCGRL_STEP16_OBS_REGS=0 builds the unit without the former.
 #include "pcgrl_step16.h"
 
 #include "../pcgrl_kernels2d.h"
@@ -250,6 +251,12 @@ __device__ inline void binary_stats_update16(const Grp<16> &g, uint32_t x, uint3
 #ifndef PCGRL_STEP16_OBS_FIRST
 #define PCGRL_STEP16_OBS_FIRST 1  // 0: encode_obs_any, the observe role as it was before encode_obs16
 #endif
+#ifndef PCGRL_STEP16_OBS_REGS
+#define PCGRL_STEP16_OBS_REGS 1  // 0: encode_obs16, the encoder of §40 (conditional border trips, byte scatter in LDS)
+#endif
+// The largest launch that takes encode_obs16_regs.  Measured faster at 4 096 and 8 192 envs and slower at 16 384 and 65 536;
+// nothing between 8 192 and 16 384 was measured, so the bound (that of the s_setprio below) is a guess inside that range.
+constexpr int STEP16_OBS_REGS_MAX_ENVS = 8192;
 #ifndef PCGRL_STEP16_OBS_PRIO
 #define PCGRL_STEP16_OBS_PRIO 0  // 1: the observe wave at the simulate wave's issue priority up to its last observation store
 #endif
@@ -357,6 +364,133 @@ __device__ inline void encode_obs16(const Grp<16> &g, const Params &p, int env, 
   }
 }
 
+// ---- encode_obs16_regs (PCGRL_STEP16_OBS_REGS): the same bytes, chunks, phases and store flavours as
+// encode_obs16 with fewer issue slots in front of the last observation store.  tools/step16_obs_regs.py restates both pieces.
+//
+// Addresses: one scalar base per wave (the observation of the wave's first env, `env0`) plus a 32-bit offset per lane and the
+// instruction's signed offset field; no 64-bit adds.
+//
+// Piece A, the border chunks: they are the cyclic range [T, T + 96) mod 192 with T = lo + 96 = 192 - 6 pos0.  Lane `row` owns
+// the chunks k = row (mod 16) as before, i.e. chunk 16 B + row of the 256-byte block B; with B0 = T >> 4 and r0 = T & 15 its
+// border chunks lie in the five blocks B0 + 1 .. B0 + 5 (mod 12) and in ONE of the two boundary blocks: B0 when row >= r0,
+// B0 + 6 otherwise.  Six unconditional stores per lane: store j >= 1 is block B0 + j for all sixteen lanes (256 contiguous,
+// 256-byte-aligned bytes, as the conditional trips wrote them), store 0 the boundary chunk.  A block index wraps
+// (B0 + j >= 12; B0 + 6 always does) by one compare on B0 and one select between two lane offsets 3072 bytes apart, the
+// 256 j in the offset field (biased by -3072 so that neither offset is negative).  Chunk 16 B + row shows pattern phase
+// (B + row) % 3 and 6 % 3 == 0, so the lane keeps the three quads rotated by (B0 + row) % 3 and store j takes quad j % 3.
+// (A first form let lane `row` store its j-th border chunk counted from T, (lo + d + 96 + 16 j) mod 192: the same chunks per
+// lane, but every store then straddles two blocks at a multiple of 96 bytes, and the launches of 16 384 and 65 536 envs lost
+// 3 % to it: DESIGN §41.)
+//
+// Piece B, the map rows: lane `row` holds the 16 tile bits of its map row; cell c shows the bytes [0, !c, c], which sit at
+// byte s = 48 - 3 pos1 of the 96-byte row, and s % 4 = pos1 % 4.  Four cells are three dwords, made from the cells' bits as
+// bytes (one 24-bit multiply spreads four bits over four bytes: the four shifted copies do not overlap) and their
+// complements with three v_perm_b32.  s is a multiple of 3, so the border pattern is a constant in map coordinates: the
+// dword in front of the map's 48 bytes is 0x00000100 and the one behind them 0x01000001.  Thirteen v_alignbyte_b32 over
+// [0x00000100, m0..m11, 0x01000001] with shift (4 - pos1 % 4) & 3 give the thirteen aligned dwords from dword (s - 1) >> 2
+// of the row on, written over the prefilled row.  With pos1 % 4 == 0 the shift is 0 and the first of the thirteen is the
+// border dword in FRONT of the map (dword s / 4 - 1 >= 2), which rewrites what the prefill put there; the last dword written
+// is at most dword 23, so nothing reaches the row's 16-byte pad or the next lane's row.
+// LDS banks (a write's bank is dword address % 32, conflicts count inside a 32-lane half): rows lie 28 dwords apart, so the
+// 16 lanes of an env fall on 8 banks (2-way), and two envs at the same pos1 (always, with the narrow representation) on the
+// same 8 (4-way): 13 dword writes x 4 = 52 array cycles per half, against 32 byte writes x 2 (2-way; the rotation kept the
+// envs apart) = 64 before.  Derived from the addresses, not measured.
+template <bool NT, int OFF>
+__device__ __attribute__((always_inline)) inline void store_obs16_s(uint64_t sbase, uint32_t voff, const u32x4_t &w) {
+  static_assert(OFF >= -4096 && OFF < 4096, "the offset field of a global store");
+  if constexpr (NT)
+    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1 nt\n\ts_nop 1" : : "v"(voff), "v"(w), "s"(sbase), "n"(OFF) : "memory");
+  else
+    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 " PCGRL_OBS_STORE_MODS "\n\ts_nop 1"
+                 :
+                 : "v"(voff), "v"(w), "s"(sbase), "n"(OFF)
+                 : "memory");
+}
+// store j >= 1 of piece A: `far` = the lane's offset in block B0 (+ 3072, the bias), `near` = the same twelve blocks lower
+template <bool NT, int J>
+__device__ __attribute__((always_inline)) inline void obs16_border_store(uint64_t sbase, uint32_t b0, uint32_t far, uint32_t near,
+                                                                         const u32x4_t *pat) {
+  store_obs16_s<NT, 256 * J - 3072>(sbase, b0 >= 12u - J ? near : far, pat[J % 3]);
+}
+template <bool NT>
+__device__ __attribute__((always_inline)) inline void obs16_border_regs(uint64_t sbase, uint32_t b0, uint32_t first, uint32_t far,
+                                                                        uint32_t near, const u32x4_t *pat) {
+  store_obs16_s<NT, -3072>(sbase, first, pat[0]);
+  obs16_border_store<NT, 1>(sbase, b0, far, near, pat);
+  obs16_border_store<NT, 2>(sbase, b0, far, near, pat);
+  obs16_border_store<NT, 3>(sbase, b0, far, near, pat);
+  obs16_border_store<NT, 4>(sbase, b0, far, near, pat);
+  obs16_border_store<NT, 5>(sbase, b0, far, near, pat);
+}
+template <bool NT>
+__device__ __attribute__((always_inline)) inline void obs16_map_rows_regs(uint64_t sbase, uint32_t voff, const uint4 *v) {
+  store_obs16_s<NT, 0>(sbase, voff, u32x4_t{v[0].x, v[0].y, v[0].z, v[0].w});
+  store_obs16_s<NT, 256>(sbase, voff, u32x4_t{v[1].x, v[1].y, v[1].z, v[1].w});
+  store_obs16_s<NT, 512>(sbase, voff, u32x4_t{v[2].x, v[2].y, v[2].z, v[2].w});
+  store_obs16_s<NT, 768>(sbase, voff, u32x4_t{v[3].x, v[3].y, v[3].z, v[3].w});
+  store_obs16_s<NT, 1024>(sbase, voff, u32x4_t{v[4].x, v[4].y, v[4].z, v[4].w});
+  store_obs16_s<NT, 1280>(sbase, voff, u32x4_t{v[5].x, v[5].y, v[5].z, v[5].w});
+}
+
+// env0: the first env of the wave (wave-uniform); lane l belongs to env0 + l / 16
+__device__ inline void encode_obs16_regs(const Grp<16> &g, const Params &p, int env0, bool active, const uint32_t *b, const int *pos,
+                                         uint8_t *lds) {
+  constexpr int C = 3, FCH = 6, STRIDE = FCH * 16 + 16, ENV_BYTES = 32 * 32 * C;
+  const bool nt = (p.obs16 & 2) != 0;  // (wave-uniform: scalar branches)
+  const uint64_t sbase = (uint64_t)(p.obs + (size_t)env0 * ENV_BYTES);
+  // (24-bit multiplies throughout: the compiler takes v_mad_u64_u32, a quarter-rate instruction, for the plain products)
+  const uint32_t d = (__umul24((uint32_t)pos[0], 6u) + (uint32_t)g.row) & 15u;
+  const uint32_t c = __umul24((uint32_t)(16 - pos[0]), 6u) + d;                     // lo + d: the lane's first map-row chunk
+  const uint32_t voff = __umul24((uint32_t)(g.lane >> 4), ENV_BYTES) + 16u * c;  // ... and its distance from sbase
+  if (active) {
+    const uint32_t T = 192u - __umul24((uint32_t)pos[0], 6u), b0 = T >> 4, r0 = T & 15u;
+    const uint32_t x = b0 + (uint32_t)g.row;                             // < 32, where x / 3 == (11 x) >> 5
+    const uint32_t ph = x - 3u * (__umul24(x, 11u) >> 5);                // (B0 + row) % 3
+    // dword `ph`, ph + 1, ph + 2 of the pattern sequence 0x01000001, 0x00010000, 0x00000100, ...: the pattern's bytes from
+    // byte ph, ph + 1 and 2 + ph on
+    const uint32_t x0 = __builtin_amdgcn_alignbyte(0x00010000u, 0x01000001u, ph);
+    const uint32_t x1 = __builtin_amdgcn_alignbyte(0x00010000u, 0x01000001u, ph + 1u);
+    const uint32_t x2 = __builtin_amdgcn_alignbyte(0x01000001u, 0x00000100u, ph);
+    const u32x4_t pat[3] = {{x0, x1, x2, x0}, {x1, x2, x0, x1}, {x2, x0, x1, x2}};
+    const uint32_t near = __umul24((uint32_t)(g.lane >> 4), ENV_BYTES) + 256u * b0 + 16u * (uint32_t)g.row;
+    const uint32_t far = near + (uint32_t)ENV_BYTES;
+    const uint32_t first = (uint32_t)g.row < r0 ? near + 6u * 256u : b0 >= 12u ? near : far;  // block B0 + 6 - 12, or B0
+    if (nt)
+      obs16_border_regs<true>(sbase, b0, first, far, near, pat);
+    else
+      obs16_border_regs<false>(sbase, b0, first, far, near, pat);
+  }
+  uint8_t *row = lds + g.lane * STRIDE;
+#pragma unroll
+  for (int q = 0; q < FCH; q++) *(uint4 *)(row + q * 16) = oob_chunk<C>(q % C);
+  uint32_t m[14];
+  m[0] = 0x00000100u;
+  m[13] = 0x01000001u;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const uint32_t spread = __umul24((b[0] >> (4 * q)) & 15u, 0x204081u);  // bit i of the four at bit 8 i (and junk elsewhere)
+    const uint32_t solid = spread & 0x01010101u, empty = solid ^ 0x01010101u;
+    m[3 * q + 1] = __builtin_amdgcn_perm(empty, solid, 0x0c00040cu);  // [0, !c0, c0, 0]
+    m[3 * q + 2] = __builtin_amdgcn_perm(empty, solid, 0x060c0105u);  // [!c1, c1, 0, !c2]
+    m[3 * q + 3] = __builtin_amdgcn_perm(empty, solid, 0x03070c02u);  // [c2, 0, !c3, c3]
+  }
+  const uint32_t sh = (uint32_t)(-pos[1]) & 3u;
+  uint32_t *w = (uint32_t *)row + ((__mul24(pos[1], -3) + 47) >> 2);
+#pragma unroll
+  for (int i = 0; i < 13; i++) w[i] = __builtin_amdgcn_alignbyte(m[i + 1], m[i], sh);
+  if (active) {
+    const uint32_t m0 = (d >= 6u ? 1u : 0u) + (d >= 12u ? 1u : 0u), q0 = d - 6u * m0;
+    const uint8_t *s0 = lds + g.gbase * STRIDE + 16 * (d + m0);
+    const uint8_t *s1 = s0 + (q0 >= 2u ? 16 : 0), *s2 = s0 + (q0 >= 4u ? 16 : 0);
+    const uint4 v[6] = {*(const uint4 *)s0,         *(const uint4 *)(s1 + 288),  *(const uint4 *)(s2 + 592),
+                        *(const uint4 *)(s0 + 896), *(const uint4 *)(s1 + 1184), *(const uint4 *)(s2 + 1488)};
+    if (nt)
+      obs16_map_rows_regs<true>(sbase, voff, v);
+    else
+      obs16_map_rows_regs<false>(sbase, voff, v);
+  }
+}
+
 // One workgroup = STEP16_PAIRS x (simulate wave, observe wave) over four envs each, as in step_kernel.  The role is decided
 // first; each role asks for all it needs of the old state in one batch and then meets the other at the barrier (the simulate
 // wave overwrites that state at its end).
@@ -408,7 +542,14 @@ __global__ __launch_bounds__(128 * STEP16_PAIRS, PCGRL_STEP_WAVES) void step16_k
       obs_rp.load(rng_stash + 4);
       reset_from_rng<PROB, LPE, M>(g, p, e, do_reset, b, pos, /*commit=*/false, nullptr, &obs_rp, &obs_rr);
     }
-#if PCGRL_STEP16_OBS_FIRST
+#if PCGRL_STEP16_OBS_FIRST && PCGRL_STEP16_OBS_REGS
+    // (the register encoder where a SIMD holds few waves and the launch waits for the observe waves' issue slots; from
+    // 16 384 envs on the launch is bound by its writes and measured 1 - 2 % faster with encode_obs16: DESIGN §41)
+    if (p.n_envs <= STEP16_OBS_REGS_MAX_ENVS)
+      encode_obs16_regs(g, p, (int)((blockIdx.x * STEP16_PAIRS + pair) * EPW), active, b, pos, lds);
+    else
+      encode_obs16(g, p, e, active, b, pos, lds);
+#elif PCGRL_STEP16_OBS_FIRST
     encode_obs16(g, p, e, active, b, pos, lds);
 #else
     encode_obs_any<PROB, LPE, true, M>(g, p, e, active, b, pos, lds);

@@ -7,8 +7,10 @@
 //   * path sweeps that run every trip without the per-level bookkeeping and derive length, last level and visited set from
 //     the frontiers of the group's last live trip (sweep16),
 //   * the env record read and written back with 16-byte accesses,
-//   * an observation encoder of its own (encode_obs16): the chunks of the rows outside the map stored from registers first,
-//     the map rows through LDS behind them.
+//   * an observation encoder of its own: the chunks of the rows outside the map stored from registers first, the map rows
+//     through LDS behind them.  Launches of up to 8 192 envs take encode_obs16_regs (six unconditional border stores per lane
+//     off one scalar base, the map part of a row built in registers and written to LDS as dwords), larger ones encode_obs16
+//     (conditional border trips, byte scatter), which the write-bound launches measured faster with.
 // The host routes a step launch here when step16_applies() holds; every other launch takes launch_binary32 as before.
 #pragma once
 #include <hip/hip_runtime.h>
