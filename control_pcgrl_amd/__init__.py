@@ -39,6 +39,10 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   NcaGenerator             the NCA level generator (the reference's default `--model NCA --representation cellular`): G
                            genomes x S seeds rolled out to their final maps in one launch, bit for bit the numpy twins of
                            control_pcgrl_amd.nca; generator_for(evaluator_or_env) builds the one for an evaluator's maps
+  GenomeArchive            the same archive with a genome (float32 [P]) as the elite: ask() hands out Gaussian children with
+                           stated arithmetic, sample() the first generation; aggregate() is simulate's fold over a genome's
+                           seeds; NcaEvolution chains ask -> generate -> score -> aggregate -> add with no host sync
+                           (control_pcgrl_amd.evo has the numpy twins)
   obs_format="codes"       any of them hands out the tile-code observation (one byte per cell); codes_to_onehot()
                            restores the one-hot image on the device
 The compute lives in csrc/libpcgrl_amd.so (hand-written HIP for gfx950) behind the C ABI of
@@ -64,3 +68,19 @@ from . import nca  # noqa: F401
 from .nca import NcaGenerator, generator_for  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number
+
+# The evolution layer (evo.py) is imported at first use, so that importing the package for the env engine alone does what it
+# did before that layer existed: `from control_pcgrl_amd import GenomeArchive` and `control_pcgrl_amd.evo` work as usual.
+_EVO_EXPORTS = ("GenomeArchive", "NcaEvolution", "aggregate", "evaluator_score", "genome_archive_for")
+
+
+def __getattr__(name):
+    if name == "evo" or name in _EVO_EXPORTS:
+        import importlib
+        module = importlib.import_module(".evo", __name__)
+        return module if name == "evo" else getattr(module, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def __dir__():
+    return sorted(list(globals()) + ["evo"] + list(_EVO_EXPORTS))

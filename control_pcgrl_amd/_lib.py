@@ -29,7 +29,7 @@ HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_c
            "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
            "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h",
            "playthrough/pcgrl_playthrough.h", "ddave/pcgrl_ddave.h", "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h",
-           "archive/pcgrl_archive.h", "mc3d_holey/pcgrl_mc3d_holey.h", "nca/pcgrl_nca.h"]
+           "archive/pcgrl_archive.h", "mc3d_holey/pcgrl_mc3d_holey.h", "nca/pcgrl_nca.h", "evo/pcgrl_evo.h"]
 SOURCES = UNITS + HEADERS
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
 CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
@@ -55,6 +55,7 @@ MDUNGEON_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mdu
 ARCHIVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_archive.h")
 MC3D_HOLEY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mc3d_holey.h")
 NCA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_nca.h")
+EVO_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_evo.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -432,6 +433,19 @@ NCA_SYMBOLS = {
     "pcgrl_nca_last_error": (C.c_char_p, []),
 }
 
+# include/pcgrl_amd_evo.h: NCA evolution (genome archives on the archive's handle, Gaussian children, simulate's fold over seeds;
+# the kernels are csrc/evo/pcgrl_evo.h, compiled into the archive's unit so that the insertion is written once)
+PCGRL_EVO_MAX_PARAMS = 16384
+PCGRL_EVO_MAX_SEEDS = 128
+PCGRL_EVO_MAX_BEHAVIOURS = 4
+EVO_SYMBOLS = {
+    "pcgrl_archive_create_genomes": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "pcgrl_archive_ask_genomes": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_float] + [C.c_void_p] * 3),
+    "pcgrl_archive_sample_genomes": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_float] + [C.c_void_p] * 3),
+    "pcgrl_evo_aggregate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 9),
+}
+
 
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
@@ -445,7 +459,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                                                        SMB_MEASURES_HEADER, LODERUNNER_HEADER,
                                                        LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER,
                                                        MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER, ARCHIVE_HEADER,
-                                                       MC3D_HOLEY_HEADER, NCA_HEADER]
+                                                       MC3D_HOLEY_HEADER, NCA_HEADER, EVO_HEADER]
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -463,7 +477,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
                    os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
                    os.path.getmtime(LODERUNNER_ROUTES_HEADER), os.path.getmtime(MICROSTRUCTURE_HEADER),
                    os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER), os.path.getmtime(ARCHIVE_HEADER),
-                   os.path.getmtime(MC3D_HOLEY_HEADER), os.path.getmtime(NCA_HEADER))
+                   os.path.getmtime(MC3D_HOLEY_HEADER), os.path.getmtime(NCA_HEADER), os.path.getmtime(EVO_HEADER))
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -518,7 +532,7 @@ def lib():
                                   + list(LODERUNNER_ROUTES_SYMBOLS.items()) + list(MICROSTRUCTURE_SYMBOLS.items())
                                   + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())
                                   + list(ARCHIVE_SYMBOLS.items()) + list(MC3D_HOLEY_SYMBOLS.items())
-                                  + list(NCA_SYMBOLS.items())):
+                                  + list(NCA_SYMBOLS.items()) + list(EVO_SYMBOLS.items())):
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

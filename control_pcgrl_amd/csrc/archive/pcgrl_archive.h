@@ -8,6 +8,10 @@
 //   win   int32   INT32_MAX
 // Both hold between calls, so an add seeds nothing: the key pass raises `word`, the commit pass puts `win` back.
 //
+// A genome archive (include/pcgrl_amd_evo.h, evo/pcgrl_evo.h) is the same archive with T = 0 and a row of L = 4 P bytes, the P
+// float32 weights of an NCA genome (L up to 65536): every kernel below copies a row as bytes and serves it unchanged; only
+// arch_ask_kernel, which flips tiles, is refused for it on the host.
+//
 // pcgrl_archive_add, kernels on one stream (a kernel boundary is the only barrier):
 //   arch_key_kernel     thread per candidate: its cell (placement, or the caller's index) into the caller's d_cell, -1 and
 //                       status 3 and error bit 0 when refused; 64-bit atomicMax of its key into word[cell]

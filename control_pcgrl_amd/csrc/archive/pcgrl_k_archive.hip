@@ -10,6 +10,8 @@
 #include <string>
 
 #include "../../../include/pcgrl_amd_archive.h"
+#include "../../../include/pcgrl_amd_evo.h"
+#include "../evo/pcgrl_evo.h"
 
 namespace pcgrl {
 
@@ -62,6 +64,19 @@ hipError_t launch_arch_export_header(const ArchGrid &g, const ArchMem &m, void *
 
 hipError_t launch_arch_import_finish(const ArchGrid &g, const ArchMem &m, const void *image, hipStream_t s) {
   hipLaunchKernelGGL(arch_import_finish_kernel, dim3(arch_blocks(g.cells)), dim3(256), 0, s, g, m, (const ArchHeader *)image);
+  return hipGetLastError();
+}
+
+hipError_t launch_evo_children(const EvoChildrenArgs &a, hipStream_t s) {
+  const int per = (a.P + EVO_EPT - 1) / EVO_EPT;  // threads that have an element
+  const int block = per >= EVO_BLOCK ? EVO_BLOCK : (per + 63) / 64 * 64;
+  hipLaunchKernelGGL(evo_children_kernel, dim3(a.n, (a.P + block * EVO_EPT - 1) / (block * EVO_EPT)), dim3(block), 0, s, a);
+  hipLaunchKernelGGL(evo_bump_kernel, dim3(1), dim3(64), 0, s, a.m, a.with_parent);
+  return hipGetLastError();
+}
+
+hipError_t launch_evo_aggregate(const EvoAggregateArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(evo_aggregate_kernel, dim3((a.G + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -120,9 +135,9 @@ extern "C" {
 
 const char *pcgrl_archive_last_error(void) { return g_arch_err.c_str(); }
 
-int pcgrl_archive_create(int32_t n_axes, const int32_t *dims, const double *lo, const double *hi, int32_t map_bytes,
-                         int32_t n_tiles, int32_t device, void **out) {
-  const char *who = "pcgrl_archive_create";
+// map_bytes and n_tiles of a map archive, or 4 * n_params and 0 of a genome archive (already checked by the caller)
+static int arch_create(const char *who, int32_t n_axes, const int32_t *dims, const double *lo, const double *hi, int32_t map_bytes,
+                       int32_t n_tiles, int32_t device, void **out) {
   if (!dims || !lo || !hi || !out) return arch_fail(PCGRL_EINVAL, who, "dims, lo, hi and out must not be null");
   *out = nullptr;
   if (n_axes < 1 || n_axes > ARCH_MAX_AXES) return arch_fail(PCGRL_EINVAL, who, "the number of behaviour axes must be in [1, 4]");
@@ -134,8 +149,11 @@ int pcgrl_archive_create(int32_t n_axes, const int32_t *dims, const double *lo, 
     if (!std::isfinite(lo[j]) || !std::isfinite(hi[j])) return arch_fail(PCGRL_EINVAL, who, "the bounds must be finite");
     if (!(lo[j] < hi[j])) return arch_fail(PCGRL_EINVAL, who, "every axis needs lo < hi");
   }
-  if (map_bytes < 1 || map_bytes > ARCH_MAX_L) return arch_fail(PCGRL_EINVAL, who, "the map length must be in [1, 4096] bytes");
-  if (n_tiles < 1 || n_tiles > ARCH_MAX_T) return arch_fail(PCGRL_EINVAL, who, "the tile count must be in [1, 256]");
+  if (n_tiles > 0 && (map_bytes < 1 || map_bytes > ARCH_MAX_L))
+    return arch_fail(PCGRL_EINVAL, who, "the map length must be in [1, 4096] bytes");
+  if (n_tiles > ARCH_MAX_T) return arch_fail(PCGRL_EINVAL, who, "the tile count must be in [1, 256]");
+  if (n_tiles == 0 && (uint64_t)cells * (uint64_t)((map_bytes + 15) / 16 * 16) > (1ull << 32))
+    return arch_fail(PCGRL_EINVAL, who, "cells x row bytes is above 2^32");
   if (device < 0) return arch_fail(PCGRL_EINVAL, who, "device must not be negative");
 
   Archive *a = new (std::nothrow) Archive();
@@ -180,6 +198,22 @@ int pcgrl_archive_create(int32_t n_axes, const int32_t *dims, const double *lo, 
   a->tag = ARCH_MAGIC;
   *out = a;
   return PCGRL_OK;
+}
+
+int pcgrl_archive_create(int32_t n_axes, const int32_t *dims, const double *lo, const double *hi, int32_t map_bytes,
+                         int32_t n_tiles, int32_t device, void **out) {
+  const char *who = "pcgrl_archive_create";
+  if (out) *out = nullptr;
+  if (n_tiles < 1) return arch_fail(PCGRL_EINVAL, who, "the tile count must be in [1, 256]");
+  return arch_create(who, n_axes, dims, lo, hi, map_bytes, n_tiles, device, out);
+}
+
+int pcgrl_archive_create_genomes(int32_t n_axes, const int32_t *dims, const double *lo, const double *hi, int32_t n_params,
+                                 int32_t device, void **out) {
+  const char *who = "pcgrl_archive_create_genomes";
+  if (out) *out = nullptr;
+  if (n_params < 1 || n_params > EVO_MAX_PARAMS) return arch_fail(PCGRL_EINVAL, who, "the genome length must be in [1, 16384]");
+  return arch_create(who, n_axes, dims, lo, hi, 4 * n_params, 0, device, out);
 }
 
 void pcgrl_archive_destroy(void *archive) {
@@ -247,6 +281,7 @@ int pcgrl_archive_ask(void *archive, int32_t n, uint64_t seed, double rate, uint
   if (n < 1) return arch_fail(PCGRL_EINVAL, who, "n must be at least 1");
   if (!(rate >= 0.0 && rate <= 1.0)) return arch_fail(PCGRL_EINVAL, who, "rate must be in [0, 1]");
   if (!d_out_maps) return arch_fail(PCGRL_EINVAL, who, "d_out_maps must not be null");
+  if (a->g.T == 0) return arch_fail(PCGRL_EINVAL, who, "a genome archive has no tiles to flip: use pcgrl_archive_ask_genomes");
   ArchAskArgs k;
   k.g = a->g, k.m = a->m, k.n = n, k.seed = seed, k.rate = rate, k.out = d_out_maps, k.parent_cell = d_out_parent_cell;
   ARCH_HIPCHK(launch_arch_ask(k, (hipStream_t)stream));
@@ -296,7 +331,10 @@ int pcgrl_archive_import(void *archive, const void *d_image, int64_t image_bytes
     if (h.dims[j] != g.dims[j]) return arch_fail(PCGRL_EINVAL, who, "the image has other dims");
     if (h.lo[j] != g.lo[j] || h.hi[j] != g.hi[j]) return arch_fail(PCGRL_EINVAL, who, "the image has other bounds");
   }
-  if (h.L != g.L) return arch_fail(PCGRL_EINVAL, who, "the image has another map length");
+  if ((h.T == 0) != (g.T == 0))
+    return arch_fail(PCGRL_EINVAL, who, g.T == 0 ? "a map archive's image does not fit a genome archive"
+                                                 : "a genome archive's image does not fit a map archive");
+  if (h.L != g.L) return arch_fail(PCGRL_EINVAL, who, g.T == 0 ? "the image has another genome length" : "the image has another map length");
   if (h.T != g.T) return arch_fail(PCGRL_EINVAL, who, "the image has another tile count");
   const ImageLayout l = image_layout(g);
   if (image_bytes != (int64_t)l.total) return arch_fail(PCGRL_EINVAL, who, "the image has another size");
@@ -327,6 +365,53 @@ int pcgrl_archive_poll_error(void *archive, void *stream) {
     return -1;
   }
   return (int)bits;
+}
+
+static int evo_children(const char *who, int with_parent, void *archive, int32_t n, uint64_t seed, float sigma, const float *d_mean,
+                        float *d_out, int32_t *d_out_parent_cell, void *stream) {
+  Archive *a = arch_of(archive);
+  if (!a) return arch_fail(PCGRL_EINVAL, who, "null or dead archive handle");
+  if (n < 1) return arch_fail(PCGRL_EINVAL, who, "n must be at least 1");
+  if (!(sigma >= 0.0f) || !std::isfinite(sigma)) return arch_fail(PCGRL_EINVAL, who, "sigma must be finite and not negative");
+  if (!d_out || ((uintptr_t)d_out & 3u)) return arch_fail(PCGRL_EINVAL, who, "d_out is null or not 4-byte aligned");
+  if (d_mean && ((uintptr_t)d_mean & 3u)) return arch_fail(PCGRL_EINVAL, who, "d_mean is not 4-byte aligned");
+  if (a->g.T != 0)
+    return arch_fail(PCGRL_EINVAL, who, "a map archive holds no genomes: use pcgrl_archive_ask (pcgrl_archive_create_genomes "
+                                        "makes a genome archive)");
+  EvoChildrenArgs k;
+  k.g = a->g, k.m = a->m, k.n = n, k.P = a->g.L / 4, k.with_parent = with_parent, k.seed = seed, k.sigma = sigma, k.mean = d_mean;
+  k.out = d_out, k.parent_cell = d_out_parent_cell;
+  ARCH_HIPCHK(launch_evo_children(k, (hipStream_t)stream));
+  return PCGRL_OK;
+}
+
+int pcgrl_archive_ask_genomes(void *archive, int32_t n, uint64_t seed, float sigma, float *d_out, int32_t *d_out_parent_cell,
+                              void *stream) {
+  return evo_children("pcgrl_archive_ask_genomes", 1, archive, n, seed, sigma, nullptr, d_out, d_out_parent_cell, stream);
+}
+
+int pcgrl_archive_sample_genomes(void *archive, int32_t n, uint64_t seed, float sigma, const float *d_mean, float *d_out,
+                                 void *stream) {
+  return evo_children("pcgrl_archive_sample_genomes", 0, archive, n, seed, sigma, d_mean, d_out, nullptr, stream);
+}
+
+int pcgrl_evo_aggregate(int32_t n_genomes, int32_t n_seeds, int32_t n_behaviours, double weight, const double *d_objective,
+                        const double *d_behaviours, const int32_t *d_n_step, double *d_out_behaviours, double *d_out_objective,
+                        int32_t *d_out_time_penalty, double *d_out_variance_penalty, uint8_t *d_out_valid, void *stream) {
+  const char *who = "pcgrl_evo_aggregate";
+  if (n_genomes < 1) return arch_fail(PCGRL_EINVAL, who, "the number of genomes must be at least 1");
+  if (n_seeds < 1 || n_seeds > EVO_MAX_SEEDS) return arch_fail(PCGRL_EINVAL, who, "the number of seeds must be in [1, 128]");
+  if (n_behaviours < 1 || n_behaviours > EVO_MAX_BEHAVIOURS)
+    return arch_fail(PCGRL_EINVAL, who, "the number of behaviours must be in [1, 4]");
+  if (!d_objective || !d_behaviours || !d_n_step) return arch_fail(PCGRL_EINVAL, who, "the inputs must not be null");
+  if (!d_out_behaviours || !d_out_objective || !d_out_time_penalty || !d_out_variance_penalty || !d_out_valid)
+    return arch_fail(PCGRL_EINVAL, who, "the outputs must not be null");
+  EvoAggregateArgs k;
+  k.G = n_genomes, k.S = n_seeds, k.D = n_behaviours, k.weight = weight, k.objective = d_objective, k.behaviours = d_behaviours;
+  k.n_step = d_n_step, k.out_behaviours = d_out_behaviours, k.out_objective = d_out_objective, k.out_time = d_out_time_penalty;
+  k.out_variance = d_out_variance_penalty, k.out_valid = d_out_valid;
+  ARCH_HIPCHK(launch_evo_aggregate(k, (hipStream_t)stream));
+  return PCGRL_OK;
 }
 
 }  // extern "C"

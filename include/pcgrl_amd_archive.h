@@ -49,6 +49,10 @@
  * PCGRL_EINVAL) and then only enqueues kernels and device-to-device copies on `stream`: no allocation, no host
  * synchronisation, HIP-graph capturable.  pcgrl_archive_poll_error alone synchronises.  All data pointers are device
  * pointers; d_maps may have any alignment.  pcgrl_archive_last_error returns this thread's last message of these calls.
+ *
+ * pcgrl_amd_evo.h makes archives of the same handle type whose payload row is an NCA genome (float32 [P]) instead of a map;
+ * every call here but pcgrl_archive_ask serves them with that row where it says d_maps.  Nothing a map archive returns, its
+ * image included, differs for it.
  */
 #ifndef PCGRL_AMD_ARCHIVE_H
 #define PCGRL_AMD_ARCHIVE_H
