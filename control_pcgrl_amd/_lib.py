@@ -7,55 +7,52 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libpcgrl_amd.so")
-# translation units (compiled in parallel, see csrc/pcgrl_dispatch.h) and the headers they depend on
-UNITS = ["pcgrl_engine.hip", "pcgrl_k_binary32.hip", "pcgrl_k_binary64.hip", "pcgrl_k_zelda32.hip", "pcgrl_k_zelda64.hip",
-         "pcgrl_k_sokoban32_8.hip", "pcgrl_k_sokoban32_16.hip", "pcgrl_k_sokoban32_32.hip",
-         "pcgrl_k_sokoban32_64.hip", "pcgrl_k_sokoban64_32.hip", "pcgrl_k_sokoban64_64.hip", "pcgrl_k_3d.hip",
-         "codes/pcgrl_codes.hip", "reps3d/pcgrl_k_3d_turtle.hip", "reps3d/pcgrl_k_3d_wide.hip",
-         "async3d/pcgrl_k_3d_async.hip", "paths/pcgrl_k_paths_binary.hip", "paths/pcgrl_k_paths_zelda.hip",
-         "solutions/pcgrl_k_solutions.hip", "multiagent/pcgrl_k_ma_binary.hip", "multiagent/pcgrl_k_ma_zelda.hip",
-         "measures/pcgrl_k_measures.hip", "smb/pcgrl_k_smb.hip", "smb/pcgrl_k_smb_env.hip", "smb/pcgrl_k_smb_ready.hip",
-         "smb/pcgrl_k_smb_state.hip", "smb/pcgrl_k_smb_rollout.hip", "smb/pcgrl_k_smb_vector.hip",
-         "smb/pcgrl_k_smb_measures.hip", "loderunner/pcgrl_k_loderunner.hip",
-         "loderunner/pcgrl_k_loderunner_measures.hip", "loderunner/pcgrl_k_loderunner_routes.hip",
-         "microstructure/pcgrl_k_microstructure.hip", "ddave/pcgrl_k_ddave.hip",
-         "mdungeon/pcgrl_k_mdungeon.hip", "step16/pcgrl_k_step16.hip", "archive/pcgrl_k_archive.hip",
-         "mc3d_holey/pcgrl_k_mc3d_holey.hip", "nca/pcgrl_k_nca.hip"]
-HEADERS = ["pcgrl_kernels2d.h", "pcgrl_kernels3d.h", "pcgrl_sokoban.h", "pcgrl_common.h", "pcgrl_dispatch.h", "codes/pcgrl_codes.h",
-           "reps3d/pcgrl_reps3d.h", "async3d/pcgrl_async3d.h", "paths/pcgrl_paths.h",
-           "solutions/pcgrl_solutions.h", "multiagent/pcgrl_multiagent.h", "measures/pcgrl_measures.h",
-           "smb/pcgrl_smb.h", "smb/pcgrl_smb_env.h", "smb/pcgrl_smb_ready.h", "smb/pcgrl_smb_state.h",
-           "smb/pcgrl_smb_rollout.h", "smb/pcgrl_smb_ctrl.h", "smb/pcgrl_smb_vector.h", "smb/pcgrl_smb_measures.h",
-           "loderunner/pcgrl_loderunner.h", "measures/pcgrl_measures_wave.h", "loderunner/pcgrl_loderunner_measures.h",
-           "loderunner/pcgrl_loderunner_routes.h", "microstructure/pcgrl_microstructure.h",
-           "playthrough/pcgrl_playthrough.h", "ddave/pcgrl_ddave.h", "mdungeon/pcgrl_mdungeon.h", "step16/pcgrl_step16.h",
-           "archive/pcgrl_archive.h", "mc3d_holey/pcgrl_mc3d_holey.h", "nca/pcgrl_nca.h", "evo/pcgrl_evo.h"]
+
+
+def _csrc_files(ext):
+    """the files of that extension under csrc/, relative with forward slashes, sorted; build directories (_obj*) left out"""
+    found = []
+    for root, dirs, files in os.walk(CSRC):
+        dirs[:] = [d for d in dirs if not d.startswith("_obj")]
+        found += [os.path.relpath(os.path.join(root, f), CSRC).replace(os.sep, "/") for f in files if f.endswith(ext)]
+    return sorted(found)
+
+
+# translation units (compiled in parallel, see csrc/pcgrl_dispatch.h) and the headers they depend on: every file under csrc/
+UNITS = _csrc_files(".hip")
+HEADERS = _csrc_files(".h")
 SOURCES = UNITS + HEADERS
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd.h")
-CODES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_codes.h")
-ASYNC3D_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_async3d.h")
-PATHS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_paths.h")
-SOLUTIONS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_solutions.h")
-MULTIAGENT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_multiagent.h")
-MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_measures.h")
-SMB_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb.h")
-SMB_ENV_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_env.h")
-SMB_READY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_ready.h")
-SMB_STATE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_state.h")
-SMB_ROLLOUT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_rollout.h")
-SMB_CTRL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_ctrl.h")
-SMB_VECTOR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_vector.h")
-SMB_MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_smb_measures.h")
-LODERUNNER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner.h")
-LODERUNNER_MEASURES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner_measures.h")
-LODERUNNER_ROUTES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_loderunner_routes.h")
-MICROSTRUCTURE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_microstructure.h")
-DDAVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_ddave.h")
-MDUNGEON_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mdungeon.h")
-ARCHIVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_archive.h")
-MC3D_HOLEY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_mc3d_holey.h")
-NCA_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_nca.h")
-EVO_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcgrl_amd_evo.h")
+
+
+def _include(name):
+    return os.path.join(os.path.dirname(_HERE), "include", name)
+
+
+HEADER = _include("pcgrl_amd.h")
+CODES_HEADER = _include("pcgrl_amd_codes.h")
+ASYNC3D_HEADER = _include("pcgrl_amd_async3d.h")
+PATHS_HEADER = _include("pcgrl_amd_paths.h")
+SOLUTIONS_HEADER = _include("pcgrl_amd_solutions.h")
+MULTIAGENT_HEADER = _include("pcgrl_amd_multiagent.h")
+MEASURES_HEADER = _include("pcgrl_amd_measures.h")
+SMB_HEADER = _include("pcgrl_amd_smb.h")
+SMB_ENV_HEADER = _include("pcgrl_amd_smb_env.h")
+SMB_READY_HEADER = _include("pcgrl_amd_smb_ready.h")
+SMB_STATE_HEADER = _include("pcgrl_amd_smb_state.h")
+SMB_ROLLOUT_HEADER = _include("pcgrl_amd_smb_rollout.h")
+SMB_CTRL_HEADER = _include("pcgrl_amd_smb_ctrl.h")
+SMB_VECTOR_HEADER = _include("pcgrl_amd_smb_vector.h")
+SMB_MEASURES_HEADER = _include("pcgrl_amd_smb_measures.h")
+LODERUNNER_HEADER = _include("pcgrl_amd_loderunner.h")
+LODERUNNER_MEASURES_HEADER = _include("pcgrl_amd_loderunner_measures.h")
+LODERUNNER_ROUTES_HEADER = _include("pcgrl_amd_loderunner_routes.h")
+MICROSTRUCTURE_HEADER = _include("pcgrl_amd_microstructure.h")
+DDAVE_HEADER = _include("pcgrl_amd_ddave.h")
+MDUNGEON_HEADER = _include("pcgrl_amd_mdungeon.h")
+ARCHIVE_HEADER = _include("pcgrl_amd_archive.h")
+MC3D_HOLEY_HEADER = _include("pcgrl_amd_mc3d_holey.h")
+NCA_HEADER = _include("pcgrl_amd_nca.h")
+EVO_HEADER = _include("pcgrl_amd_evo.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
 PCGRL_MAX_STATS = 8
@@ -447,19 +444,42 @@ EVO_SYMBOLS = {
 }
 
 
+# The C ABI, one entry per public header: (file under include/, its symbol table).  build() watches these headers and lib()
+# binds these tables; tests/test_abi_table_cpu.py holds each header's declarations against its table.
+ABI = [("pcgrl_amd.h", SYMBOLS),
+       ("pcgrl_amd_codes.h", CODES_SYMBOLS),
+       ("pcgrl_amd_async3d.h", ASYNC3D_SYMBOLS),
+       ("pcgrl_amd_paths.h", PATHS_SYMBOLS),
+       ("pcgrl_amd_solutions.h", SOLUTIONS_SYMBOLS),
+       ("pcgrl_amd_multiagent.h", MULTIAGENT_SYMBOLS),
+       ("pcgrl_amd_measures.h", MEASURES_SYMBOLS),
+       ("pcgrl_amd_smb.h", SMB_SYMBOLS),
+       ("pcgrl_amd_smb_env.h", SMB_ENV_SYMBOLS),
+       ("pcgrl_amd_smb_ready.h", SMB_READY_SYMBOLS),
+       ("pcgrl_amd_smb_state.h", SMB_STATE_SYMBOLS),
+       ("pcgrl_amd_smb_rollout.h", SMB_ROLLOUT_SYMBOLS),
+       ("pcgrl_amd_smb_ctrl.h", SMB_CTRL_SYMBOLS),
+       ("pcgrl_amd_smb_vector.h", SMB_VECTOR_SYMBOLS),
+       ("pcgrl_amd_smb_measures.h", SMB_MEASURES_SYMBOLS),
+       ("pcgrl_amd_loderunner.h", LODERUNNER_SYMBOLS),
+       ("pcgrl_amd_loderunner_measures.h", LODERUNNER_MEASURES_SYMBOLS),
+       ("pcgrl_amd_loderunner_routes.h", LODERUNNER_ROUTES_SYMBOLS),
+       ("pcgrl_amd_microstructure.h", MICROSTRUCTURE_SYMBOLS),
+       ("pcgrl_amd_ddave.h", DDAVE_SYMBOLS),
+       ("pcgrl_amd_mdungeon.h", MDUNGEON_SYMBOLS),
+       ("pcgrl_amd_archive.h", ARCHIVE_SYMBOLS),
+       ("pcgrl_amd_mc3d_holey.h", MC3D_HOLEY_SYMBOLS),
+       ("pcgrl_amd_nca.h", NCA_SYMBOLS),
+       ("pcgrl_amd_evo.h", EVO_SYMBOLS)]
+ABI_HEADERS = [_include(name) for name, _ in ABI]
+
+
 def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU), one object per translation unit, compiled in
     parallel, then linked into the shared library.  Rebuilds when a source is newer than the library.
     `out` / `defines`: development builds (tools/phase_timing.py, tools/wave_trace.py)."""
     out = out or LIB_PATH
-    srcs = [os.path.join(CSRC, s) for s in SOURCES] + [HEADER, CODES_HEADER, ASYNC3D_HEADER, PATHS_HEADER,
-                                                       SOLUTIONS_HEADER, MULTIAGENT_HEADER, MEASURES_HEADER, SMB_HEADER,
-                                                       SMB_ENV_HEADER, SMB_READY_HEADER, SMB_STATE_HEADER,
-                                                       SMB_ROLLOUT_HEADER, SMB_CTRL_HEADER, SMB_VECTOR_HEADER,
-                                                       SMB_MEASURES_HEADER, LODERUNNER_HEADER,
-                                                       LODERUNNER_MEASURES_HEADER, LODERUNNER_ROUTES_HEADER,
-                                                       MICROSTRUCTURE_HEADER, DDAVE_HEADER, MDUNGEON_HEADER, ARCHIVE_HEADER,
-                                                       MC3D_HOLEY_HEADER, NCA_HEADER, EVO_HEADER]
+    srcs = [os.path.join(CSRC, s) for s in SOURCES] + ABI_HEADERS
     if (not force and os.path.exists(out)
             and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s))):
         return out
@@ -467,17 +487,7 @@ def build(force=False, verbose=False, out=None, defines=(), jobs=None):
     tag = "".join(sorted(d.replace("=", "_") for d in defines))
     objdir = os.path.join(CSRC, "_obj" + ("_" + tag if tag else ""))
     os.makedirs(objdir, exist_ok=True)
-    hdr_time = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
-    hdr_time = max(hdr_time, os.path.getmtime(HEADER), os.path.getmtime(CODES_HEADER), os.path.getmtime(ASYNC3D_HEADER),
-                   os.path.getmtime(PATHS_HEADER), os.path.getmtime(SOLUTIONS_HEADER), os.path.getmtime(MULTIAGENT_HEADER),
-                   os.path.getmtime(MEASURES_HEADER), os.path.getmtime(SMB_HEADER), os.path.getmtime(SMB_ENV_HEADER),
-                   os.path.getmtime(SMB_READY_HEADER), os.path.getmtime(SMB_STATE_HEADER),
-                   os.path.getmtime(SMB_ROLLOUT_HEADER), os.path.getmtime(SMB_CTRL_HEADER),
-                   os.path.getmtime(SMB_VECTOR_HEADER), os.path.getmtime(SMB_MEASURES_HEADER),
-                   os.path.getmtime(LODERUNNER_HEADER), os.path.getmtime(LODERUNNER_MEASURES_HEADER),
-                   os.path.getmtime(LODERUNNER_ROUTES_HEADER), os.path.getmtime(MICROSTRUCTURE_HEADER),
-                   os.path.getmtime(DDAVE_HEADER), os.path.getmtime(MDUNGEON_HEADER), os.path.getmtime(ARCHIVE_HEADER),
-                   os.path.getmtime(MC3D_HOLEY_HEADER), os.path.getmtime(NCA_HEADER), os.path.getmtime(EVO_HEADER))
+    hdr_time = max(os.path.getmtime(h) for h in [os.path.join(CSRC, h) for h in HEADERS] + ABI_HEADERS)
     jobs_todo, objs = [], []
     for u in UNITS:
         obj = os.path.join(objdir, os.path.basename(u).replace(".hip", ".o"))
@@ -521,18 +531,7 @@ def lib():
         if override and os.path.dirname(os.path.realpath(override)) != os.path.realpath(CSRC):
             raise RuntimeError(f"PCGRL_LIB={override}: only libraries inside {CSRC} are loaded")
         L = C.CDLL(override or LIB_PATH)
-        for name, (res, args) in (list(SYMBOLS.items()) + list(CODES_SYMBOLS.items()) + list(ASYNC3D_SYMBOLS.items())
-                                  + list(PATHS_SYMBOLS.items()) + list(SOLUTIONS_SYMBOLS.items())
-                                  + list(MULTIAGENT_SYMBOLS.items()) + list(MEASURES_SYMBOLS.items())
-                                  + list(SMB_SYMBOLS.items()) + list(SMB_ENV_SYMBOLS.items())
-                                  + list(SMB_READY_SYMBOLS.items()) + list(SMB_STATE_SYMBOLS.items())
-                                  + list(SMB_ROLLOUT_SYMBOLS.items()) + list(SMB_CTRL_SYMBOLS.items())
-                                  + list(SMB_VECTOR_SYMBOLS.items()) + list(SMB_MEASURES_SYMBOLS.items())
-                                  + list(LODERUNNER_SYMBOLS.items()) + list(LODERUNNER_MEASURES_SYMBOLS.items())
-                                  + list(LODERUNNER_ROUTES_SYMBOLS.items()) + list(MICROSTRUCTURE_SYMBOLS.items())
-                                  + list(DDAVE_SYMBOLS.items()) + list(MDUNGEON_SYMBOLS.items())
-                                  + list(ARCHIVE_SYMBOLS.items()) + list(MC3D_HOLEY_SYMBOLS.items())
-                                  + list(NCA_SYMBOLS.items()) + list(EVO_SYMBOLS.items())):
+        for name, (res, args) in [item for _, table in ABI for item in table.items()]:
             if override and not hasattr(L, name):
                 continue
             fn = getattr(L, name)

@@ -1987,6 +1987,54 @@ static int diversity_enqueue(MeasWaveArgs a, int P, Launch launch, int32_t group
   return PCGRL_OK;
 }
 
+// The caller-map entry points of a level family (<family>_measures_for_grids, <family>_diversity_for_grids): `check_shape` is
+// the family's shape refusal, P its plane count and `launch` its measure / pack kernel.  The pointer checks come first.
+typedef int (*ShapeCheck)(const char *who, int32_t h, int32_t w);
+
+template <class Launch>
+static int measures_for_grids(const char *who, ShapeCheck check_shape, Launch launch, int32_t h, int32_t w, int32_t n,
+                              const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,
+                              const double *d_tab, void *stream) {
+  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_tab);
+  if (rc == PCGRL_OK) rc = check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch, d_counts, d_match, d_forms, d_entropy, d_tab, stream);
+}
+
+template <class Launch>
+static int diversity_for_grids(const char *who, ShapeCheck check_shape, int P, Launch launch, int32_t h, int32_t w, int32_t n,
+                               const uint8_t *d_grids, int32_t group, void *d_scratch, int64_t *d_sum, double *d_scores,
+                               int32_t *d_nearest, int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
+  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
+  if (rc == PCGRL_OK) rc = check_shape(who, h, w);
+  if (rc != PCGRL_OK || n == 0) return rc;
+  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), P, launch, group, d_scratch, d_sum, d_scores, d_nearest,
+                           d_nearest_idx, d_pairwise, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- level families: shared checks
+// What the entry points of the level families below share besides the measures.
+
+// a config's per-statistic targets and weights into the kernel's arguments, K statistics
+template <int K, class Args, class Config>
+static void copy_targets(Args &a, const Config *cfg) {
+  for (int k = 0; k < K; k++) {
+    a.has_trg[k] = cfg->has_trg[k];
+    a.weight[k] = cfg->weight[k];
+    a.trg_lo[k] = cfg->trg_lo[k];
+    a.trg_hi[k] = cfg->trg_hi[k];
+  }
+}
+
+// the caller's workspace: `align` a power of two, `needed` what `sized_by` (the function the text names) gives for the call
+static int workspace_check(const char *who, const void *d_workspace, unsigned align, int64_t given, int64_t needed,
+                           const char *sized_by) {
+  if (!d_workspace || ((uintptr_t)d_workspace & (align - 1)) || given < needed)
+    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not " + std::to_string(align) +
+                                  "-byte aligned or smaller than " + sized_by);
+  return PCGRL_OK;
+}
+
 // include/pcgrl_amd_measures.h: the 2-D engine's maps (`own`) or caller maps of its problem and shape
 static const char *MEASURES_3D =
     ": 2-D problems only (the reference's get_counts reads an attribute the 3-D maze does not have and get_co looks at two "
@@ -2207,8 +2255,10 @@ int pcgrl_ma_set_state(pcgrl_handle h, const uint8_t *d_mask, const int32_t *d_p
 
 // ---------------------------------------------------------------------------------------------- Super Mario Bros levels
 // include/pcgrl_amd_smb.h; kernel in smb/pcgrl_smb.h.  No handle: the evaluation is a function of the maps and the config.
+static bool smb_shape_ok(int32_t h, int32_t w) { return h >= SMB_MIN_H && h <= SMB_MAX_H && w >= 1 && w <= SMB_MAX_W; }
+
 static int smb_check_shape(const char *who, int32_t h, int32_t w, int32_t power) {
-  if (h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W)
+  if (!smb_shape_ok(h, w))
     return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 4..16 rows and 1..128 columns only (with fewer than 4 rows the "
                                                        "reference's level has no exit)");
   if (power < 1 || power > SMB_MAX_POWER)
@@ -2231,9 +2281,8 @@ int pcgrl_smb_evaluate(const pcgrl_smb_config *cfg, int32_t n, const uint8_t *d_
   const int rc = smb_check_shape(who, cfg->h, cfg->w, cfg->solver_power);
   if (rc != PCGRL_OK) return rc;
   const int64_t stride = smb_ws_stride(cfg->solver_power);
-  if (!d_workspace || ((uintptr_t)d_workspace & 7u) || workspace_bytes < (int64_t)n * stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 8-byte aligned or smaller than "
-                                                 "pcgrl_smb_workspace_bytes");
+  const int ws = workspace_check(who, d_workspace, 8, workspace_bytes, (int64_t)n * stride, "pcgrl_smb_workspace_bytes");
+  if (ws != PCGRL_OK) return ws;
   SmbArgs a = {};
   a.h = cfg->h;
   a.w = cfg->w;
@@ -2251,20 +2300,17 @@ int pcgrl_smb_evaluate(const pcgrl_smb_config *cfg, int32_t n, const uint8_t *d_
   a.jump_locs = d_jump_locs;
   a.play = d_play;
   a.error = d_error;
-  for (int k = 0; k < SMB_STATS; k++) {
-    a.has_trg[k] = cfg->has_trg[k];
-    a.weight[k] = cfg->weight[k];
-    a.trg_lo[k] = cfg->trg_lo[k];
-    a.trg_hi[k] = cfg->trg_hi[k];
-  }
+  copy_targets<SMB_STATS>(a, cfg);
   HIPCHK(launch_smb(a, (hipStream_t)stream));
   return PCGRL_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- Lode Runner levels
 // include/pcgrl_amd_loderunner.h; kernel in loderunner/pcgrl_loderunner.h.  No handle, as for the Mario levels above.
+static bool lr_shape_ok(int32_t h, int32_t w) { return h >= 1 && h <= LR_MAX_H && w >= 1 && w <= LR_MAX_W; }
+
 static int lr_check_shape(const char *who, int32_t h, int32_t w) {
-  if (h < 1 || h > LR_MAX_H || w < 1 || w > LR_MAX_W)
+  if (!lr_shape_ok(h, w))
     return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..16 rows and 1..32 columns only");
   return PCGRL_OK;
 }
@@ -2283,9 +2329,9 @@ static int lr_fill_args(const char *who, LrArgs &a, const pcgrl_loderunner_confi
   const int rc = lr_check_shape(who, cfg->h, cfg->w);
   if (rc != PCGRL_OK) return rc;
   const int64_t stride = lr_ws_stride(cfg->h, cfg->w);
-  if (!d_workspace || ((uintptr_t)d_workspace & 3u) || workspace_bytes < (int64_t)lr_blocks(n, cfg->h, cfg->w) * stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 4-byte aligned or smaller than "
-                                                 "pcgrl_loderunner_workspace_bytes");
+  const int ws = workspace_check(who, d_workspace, 4, workspace_bytes, (int64_t)lr_blocks(n, cfg->h, cfg->w) * stride,
+                                 "pcgrl_loderunner_workspace_bytes");
+  if (ws != PCGRL_OK) return ws;
   a = LrArgs{};
   a.h = cfg->h;
   a.w = cfg->w;
@@ -2300,12 +2346,7 @@ static int lr_fill_args(const char *who, LrArgs &a, const pcgrl_loderunner_confi
   a.gold_state = d_gold_state;
   a.gold_dist = d_gold_dist;
   a.error = d_error;
-  for (int k = 0; k < LR_STATS; k++) {
-    a.has_trg[k] = cfg->has_trg[k];
-    a.weight[k] = cfg->weight[k];
-    a.trg_lo[k] = cfg->trg_lo[k];
-    a.trg_hi[k] = cfg->trg_hi[k];
-  }
+  copy_targets<LR_STATS>(a, cfg);
   return PCGRL_OK;
 }
 
@@ -2354,28 +2395,20 @@ extern "C" {
 int pcgrl_loderunner_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
                                         int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
                                         void *stream) {
-  const char *who = "pcgrl_loderunner_measures_for_grids";
-  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = lr_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_lr_measures, d_counts, d_match, d_forms, d_entropy,
-                          d_entropy_tab, stream);
+  return measures_for_grids("pcgrl_loderunner_measures_for_grids", lr_check_shape, launch_lr_measures, h, w, n, d_grids,
+                            d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
 }
 
 size_t pcgrl_loderunner_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
-  if (n <= 0 || h < 1 || h > LR_MAX_H || w < 1 || w > LR_MAX_W) return 0;
+  if (n <= 0 || !lr_shape_ok(h, w)) return 0;
   return diversity_scratch_bytes(LR_MEAS_PLANES, h, w, n);
 }
 
 int pcgrl_loderunner_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
                                          void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
                                          int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
-  const char *who = "pcgrl_loderunner_diversity_for_grids";
-  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = lr_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), LR_MEAS_PLANES, launch_lr_measures, group, d_scratch, d_sum,
-                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_for_grids("pcgrl_loderunner_diversity_for_grids", lr_check_shape, LR_MEAS_PLANES, launch_lr_measures, h, w,
+                             n, d_grids, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"
@@ -2384,8 +2417,10 @@ int pcgrl_loderunner_diversity_for_grids(int32_t h, int32_t w, int32_t n, const 
 // include/pcgrl_amd_microstructure.h; kernels in microstructure/pcgrl_microstructure.h.  No handle and no workspace.  The
 // measures and the diversity are the (2, 1, 4096) instantiation of the wave body through the host path of "measures and
 // diversity" above.
+static bool ms_shape_ok(int32_t h, int32_t w) { return h >= 1 && h <= MS_MAX_H && w >= 1 && w <= MS_MAX_W; }
+
 static int ms_check_shape(const char *who, int32_t h, int32_t w) {
-  if (h < 1 || h > MS_MAX_H || w < 1 || w > MS_MAX_W)
+  if (!ms_shape_ok(h, w))
     return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..64 rows and 1..64 columns only");
   return PCGRL_OK;
 }
@@ -2412,12 +2447,7 @@ int pcgrl_microstructure_evaluate(const pcgrl_microstructure_config *cfg, int32_
   a.region_rec = region_cap > 0 ? d_region_rec : nullptr;
   a.region_tort = region_cap > 0 ? d_region_tort : nullptr;
   a.error = d_error;
-  for (int k = 0; k < MS_STATS; k++) {
-    a.has_trg[k] = cfg->has_trg[k];
-    a.weight[k] = cfg->weight[k];
-    a.trg_lo[k] = cfg->trg_lo[k];
-    a.trg_hi[k] = cfg->trg_hi[k];
-  }
+  copy_targets<MS_STATS>(a, cfg);
   HIPCHK(launch_microstructure(a, (hipStream_t)stream));
   return PCGRL_OK;
 }
@@ -2425,28 +2455,20 @@ int pcgrl_microstructure_evaluate(const pcgrl_microstructure_config *cfg, int32_
 int pcgrl_microstructure_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
                                             int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
                                             void *stream) {
-  const char *who = "pcgrl_microstructure_measures_for_grids";
-  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = ms_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_ms_measures, d_counts, d_match, d_forms, d_entropy,
-                          d_entropy_tab, stream);
+  return measures_for_grids("pcgrl_microstructure_measures_for_grids", ms_check_shape, launch_ms_measures, h, w, n, d_grids,
+                            d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
 }
 
 size_t pcgrl_microstructure_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
-  if (n <= 0 || h < 1 || h > MS_MAX_H || w < 1 || w > MS_MAX_W) return 0;
+  if (n <= 0 || !ms_shape_ok(h, w)) return 0;
   return diversity_scratch_bytes(MS_MEAS_PLANES, h, w, n);
 }
 
 int pcgrl_microstructure_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group,
                                              void *d_scratch, int64_t *d_sum, double *d_scores, int32_t *d_nearest,
                                              int32_t *d_nearest_idx, int32_t *d_pairwise, void *stream) {
-  const char *who = "pcgrl_microstructure_diversity_for_grids";
-  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = ms_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), MS_MEAS_PLANES, launch_ms_measures, group, d_scratch, d_sum,
-                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_for_grids("pcgrl_microstructure_diversity_for_grids", ms_check_shape, MS_MEAS_PLANES, launch_ms_measures, h,
+                             w, n, d_grids, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"
@@ -2454,8 +2476,10 @@ int pcgrl_microstructure_diversity_for_grids(int32_t h, int32_t w, int32_t n, co
 // ---------------------------------------------------------------------------------------------- solver play-throughs
 // What the entry points of the Dangerous Dave and MiniDungeon levels below share (playthrough/pcgrl_playthrough.h): `who` names
 // the caller in the error text, `ws_name` the function whose size the workspace must have, `launch` is the game's kernel.
+static bool pt_shape_ok(int32_t h, int32_t w) { return h >= 1 && h <= PT_MAX_H && w >= 1 && w <= PT_MAX_W; }
+
 static int pt_check_shape(const char *who, int32_t h, int32_t w) {
-  if (h < 1 || h > PT_MAX_H || w < 1 || w > PT_MAX_W)
+  if (!pt_shape_ok(h, w))
     return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 1..16 rows and 1..32 columns only");
   return PCGRL_OK;
 }
@@ -2485,8 +2509,8 @@ static int pt_evaluate(const char *who, const char *ws_name, hipError_t (*launch
   if (rc == PCGRL_OK) rc = pt_check_power(who, power);
   if (rc != PCGRL_OK) return rc;
   const int64_t stride = pt_ws_stride(power);
-  if (!d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < (int64_t)n * stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than " + ws_name);
+  rc = workspace_check(who, d_workspace, 16, workspace_bytes, (int64_t)n * stride, ws_name);
+  if (rc != PCGRL_OK) return rc;
   PtArgs a{};
   a.h = h;
   a.w = w;
@@ -2526,28 +2550,20 @@ int pcgrl_ddave_evaluate(const pcgrl_ddave_config *cfg, int32_t n, const uint8_t
 
 int pcgrl_ddave_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
                                    double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
-  const char *who = "pcgrl_ddave_measures_for_grids";
-  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_dd_measures, d_counts, d_match, d_forms, d_entropy,
-                          d_entropy_tab, stream);
+  return measures_for_grids("pcgrl_ddave_measures_for_grids", pt_check_shape, launch_dd_measures, h, w, n, d_grids, d_counts,
+                            d_match, d_forms, d_entropy, d_entropy_tab, stream);
 }
 
 size_t pcgrl_ddave_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
-  if (n <= 0 || h < 1 || h > DD_MAX_H || w < 1 || w > DD_MAX_W) return 0;
+  if (n <= 0 || !pt_shape_ok(h, w)) return 0;
   return diversity_scratch_bytes(DD_MEAS_PLANES, h, w, n);
 }
 
 int pcgrl_ddave_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch,
                                     int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
                                     int32_t *d_pairwise, void *stream) {
-  const char *who = "pcgrl_ddave_diversity_for_grids";
-  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), DD_MEAS_PLANES, launch_dd_measures, group, d_scratch, d_sum,
-                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_for_grids("pcgrl_ddave_diversity_for_grids", pt_check_shape, DD_MEAS_PLANES, launch_dd_measures, h, w, n,
+                             d_grids, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"
@@ -2574,28 +2590,20 @@ int pcgrl_mdungeon_evaluate(const pcgrl_mdungeon_config *cfg, int32_t n, const u
 int pcgrl_mdungeon_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts,
                                       int32_t *d_match, double *d_forms, double *d_entropy, const double *d_entropy_tab,
                                       void *stream) {
-  const char *who = "pcgrl_mdungeon_measures_for_grids";
-  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_md_measures, d_counts, d_match, d_forms, d_entropy,
-                          d_entropy_tab, stream);
+  return measures_for_grids("pcgrl_mdungeon_measures_for_grids", pt_check_shape, launch_md_measures, h, w, n, d_grids,
+                            d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
 }
 
 size_t pcgrl_mdungeon_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
-  if (n <= 0 || h < 1 || h > MD_MAX_H || w < 1 || w > MD_MAX_W) return 0;
+  if (n <= 0 || !pt_shape_ok(h, w)) return 0;
   return diversity_scratch_bytes(MD_MEAS_PLANES, h, w, n);
 }
 
 int pcgrl_mdungeon_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch,
                                        int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
                                        int32_t *d_pairwise, void *stream) {
-  const char *who = "pcgrl_mdungeon_diversity_for_grids";
-  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = pt_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), MD_MEAS_PLANES, launch_md_measures, group, d_scratch, d_sum,
-                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_for_grids("pcgrl_mdungeon_diversity_for_grids", pt_check_shape, MD_MEAS_PLANES, launch_md_measures, h, w, n,
+                             d_grids, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 }  // extern "C"
@@ -2633,9 +2641,9 @@ int pcgrl_mc3d_holey_evaluate(const pcgrl_mc3d_holey_config *cfg, int32_t n, con
   if (rc != PCGRL_OK) return rc;
   const int cells = h3_cells(cfg->z, cfg->y, cfg->x);
   const int64_t stride = h3_ws_stride(cells);
-  if (!d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 16-byte aligned or smaller than "
-                                                 "pcgrl_mc3d_holey_workspace_bytes(1, z, y, x)");
+  const int ws =
+      workspace_check(who, d_workspace, 16, workspace_bytes, stride, "pcgrl_mc3d_holey_workspace_bytes(1, z, y, x)");
+  if (ws != PCGRL_OK) return ws;
   H3Args a{};
   a.problem = cfg->problem;
   a.Z = cfg->z, a.Y = cfg->y, a.X = cfg->x;
@@ -2721,9 +2729,9 @@ int pcgrl_smb_env_create(const pcgrl_smb_env_config *cfg, int32_t device, void *
   const int rc = smb_env_check(who, cfg);
   if (rc != PCGRL_OK) return rc;
   const int64_t stride = smb_ws_stride(cfg->solver_power);
-  if (!d_workspace || ((uintptr_t)d_workspace & 7u) || workspace_bytes < (int64_t)cfg->n_envs * stride)
-    return fail(PCGRL_EINVAL, std::string(who) + ": the workspace is null, not 8-byte aligned or smaller than "
-                                                 "pcgrl_smb_env_workspace_bytes");
+  const int ws = workspace_check(who, d_workspace, 8, workspace_bytes, (int64_t)cfg->n_envs * stride,
+                                 "pcgrl_smb_env_workspace_bytes");
+  if (ws != PCGRL_OK) return ws;
   if (device < 0) return fail(PCGRL_EINVAL, std::string(who) + ": bad device");
   ON_DEVICE(device);
   pcgrl_smb_env *e = new pcgrl_smb_env();
@@ -2744,12 +2752,7 @@ int pcgrl_smb_env_create(const pcgrl_smb_env_config *cfg, int32_t device, void *
   a.map_stride = (cfg->h * cfg->w + 15) / 16 * 16;
   a.ws = (uint8_t *)d_workspace;
   a.ws_stride = stride;
-  for (int k = 0; k < SMB_STATS; k++) {
-    a.has_trg[k] = cfg->has_trg[k];
-    a.weight[k] = cfg->weight[k];
-    a.trg_lo[k] = cfg->trg_lo[k];
-    a.trg_hi[k] = cfg->trg_hi[k];
-  }
+  copy_targets<SMB_STATS>(a, cfg);
   const int cells = cfg->h * cfg->w, cpl = (cells + 63) / 64;
   const std::vector<JumpEntry> jt = make_jump_table(64, cpl, cells);
   const size_t n = (size_t)cfg->n_envs;
@@ -3403,7 +3406,7 @@ int pcgrl_smb_env_observe_f32(pcgrl_smb_env_handle h, float *out, void *stream) 
 // measures/pcgrl_measures.h; the host path is the one of "measures and diversity" above.
 
 static int smb_meas_check_shape(const char *who, int32_t h, int32_t w) {
-  if (h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W)
+  if (!smb_shape_ok(h, w))
     return fail(PCGRL_EUNSUPPORTED, std::string(who) + ": maps of 4..16 rows and 1..128 columns only (the shapes the smb "
                                                        "evaluator takes)");
   return PCGRL_OK;
@@ -3418,28 +3421,20 @@ extern "C" {
 
 int pcgrl_smb_measures_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t *d_counts, int32_t *d_match,
                                  double *d_forms, double *d_entropy, const double *d_entropy_tab, void *stream) {
-  const char *who = "pcgrl_smb_measures_for_grids";
-  int rc = measures_check(who, true, n, d_grids, d_counts, d_match, d_entropy, d_entropy_tab);
-  if (rc == PCGRL_OK) rc = smb_meas_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return measures_enqueue(meas_args(d_grids, h * w, h, w, n), launch_smb_measures, d_counts, d_match, d_forms, d_entropy,
-                          d_entropy_tab, stream);
+  return measures_for_grids("pcgrl_smb_measures_for_grids", smb_meas_check_shape, launch_smb_measures, h, w, n, d_grids,
+                            d_counts, d_match, d_forms, d_entropy, d_entropy_tab, stream);
 }
 
 size_t pcgrl_smb_diversity_scratch_bytes(int32_t h, int32_t w, int32_t n) {
-  if (n <= 0 || h < SMB_MIN_H || h > SMB_MAX_H || w < 1 || w > SMB_MAX_W) return 0;
+  if (n <= 0 || !smb_shape_ok(h, w)) return 0;
   return diversity_scratch_bytes(SMB_MEAS_PLANES, h, w, n);
 }
 
 int pcgrl_smb_diversity_for_grids(int32_t h, int32_t w, int32_t n, const uint8_t *d_grids, int32_t group, void *d_scratch,
                                   int64_t *d_sum, double *d_scores, int32_t *d_nearest, int32_t *d_nearest_idx,
                                   int32_t *d_pairwise, void *stream) {
-  const char *who = "pcgrl_smb_diversity_for_grids";
-  int rc = diversity_check(who, true, n, d_grids, group, d_scratch, d_sum);
-  if (rc == PCGRL_OK) rc = smb_meas_check_shape(who, h, w);
-  if (rc != PCGRL_OK || n == 0) return rc;
-  return diversity_enqueue(meas_args(d_grids, h * w, h, w, n), SMB_MEAS_PLANES, launch_smb_measures, group, d_scratch, d_sum,
-                           d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
+  return diversity_for_grids("pcgrl_smb_diversity_for_grids", smb_meas_check_shape, SMB_MEAS_PLANES, launch_smb_measures, h, w,
+                             n, d_grids, group, d_scratch, d_sum, d_scores, d_nearest, d_nearest_idx, d_pairwise, stream);
 }
 
 int pcgrl_smb_env_measures(pcgrl_smb_env_handle h, int32_t *d_counts, int32_t *d_match, double *d_forms, double *d_entropy,

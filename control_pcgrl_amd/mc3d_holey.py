@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .problems import ProblemSpec, target_interval
+from .evaluator import EvaluatorCore
+from .problems import ProblemSpec, fill_targets
 
 MC3D_HOLEY_PROBLEMS = {"dungeon": 0, "maze": 1}
 MC3D_HOLEY_TILES = {"dungeon": ["AIR", "DIRT", "CHEST", "SKULL", "PUMPKIN"], "maze": ["AIR", "DIRT"]}
@@ -61,18 +62,10 @@ def mc3d_holey_spec(problem="dungeon", map_shape=(7, 7, 7)) -> ProblemSpec:
 def mc3d_holey_config(problem="dungeon", map_shape=(7, 7, 7), weights=None) -> "_lib.PcgrlMc3dHoleyConfig":
     """The C config of include/pcgrl_amd_mc3d_holey.h: the frozen targets as zero-loss intervals, and the weights."""
     spec = mc3d_holey_spec(problem, map_shape)
-    weights = dict(spec.default_weights) if weights is None else dict(weights)
-    unknown = set(weights) - set(spec.stat_keys)
-    if unknown:
-        raise ValueError(f"unknown statistics in weights: {sorted(unknown)}")
     cfg = _lib.PcgrlMc3dHoleyConfig()
     cfg.problem = MC3D_HOLEY_PROBLEMS[problem]
     cfg.z, cfg.y, cfg.x = (int(s) for s in map_shape)
-    for i, k in enumerate(spec.stat_keys):
-        lo, hi = target_interval(spec.static_trgs[k])
-        cfg.weight[i] = float(weights.get(k, 0.0))
-        cfg.trg_lo[i], cfg.trg_hi[i] = lo, hi
-    return cfg
+    return fill_targets(cfg, spec, weights)
 
 
 def hole_ok(foot, map_shape):
@@ -107,19 +100,20 @@ def all_holes(map_shape=(7, 7, 7)):
     return np.ascontiguousarray(np.stack([a[ok], b[ok]], axis=1))
 
 
-class Mc3dHoleyEvaluator:
+class Mc3dHoleyEvaluator(EvaluatorCore):
     """Evaluates batches of 3-D holey dungeon or maze levels (interiors of 3..16 cells an axis) on one device.  Owns the search
     workspace, allocated once: one slot per workgroup of a launch (two rings of 8 bytes times the power of two >= 8 * bordered
     cells, and above 8^3 the per-cell search state: 128 KiB a slot at 7^3, 1.08 MiB at 15^3 and 16^3); `max_blocks` workgroups
-    (None: 2048, fewer when that would pass 1 GiB) stride over the levels of a launch.  No host sync and no CPU fallback."""
+    (None: 2048, fewer when that would pass 1 GiB) stride over the levels of a launch.  No host sync and no CPU fallback.
+    Of the evaluators' shared code (evaluator.py) it has what needs no table: one launch covers a batch, there are three error
+    bits and no measures."""
+
+    RANK = 3
 
     def __init__(self, problem="dungeon", map_shape=(7, 7, 7), device="cuda:0", weights=None, max_blocks=None):
-        self._L = _lib.lib()
         if problem not in MC3D_HOLEY_PROBLEMS:
             raise ValueError(f"unknown problem {problem!r}: 'dungeon' or 'maze'")
-        map_shape = tuple(int(s) for s in map_shape)
-        if len(map_shape) != 3:
-            raise ValueError(f"the holey levels are 3-D, got shape {map_shape}")
+        map_shape = self._map_shape_arg(map_shape, "the holey levels")
         self.problem, self.map_shape = problem, map_shape
         self.spec = mc3d_holey_spec(problem, map_shape)
         self.stat_keys = list(self.spec.stat_keys)
@@ -133,27 +127,9 @@ class Mc3dHoleyEvaluator:
         self.max_blocks = int(max_blocks)
         self._cfg = mc3d_holey_config(problem, map_shape, weights)
         self.weights = {k: self._cfg.weight[i] for i, k in enumerate(self.stat_keys)}
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("Mc3dHoleyEvaluator needs a cuda device: there is no CPU fallback")
+        self._open(device)
         self._workspace_bytes = slot * self.max_blocks
         self._workspace = torch.empty(self._workspace_bytes // 8, dtype=torch.int64, device=self.device)
-        self._error = torch.zeros(1, dtype=torch.int32, device=self.device)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _grids_arg(self, grids):
-        if self._workspace is None:
-            raise RuntimeError("Mc3dHoleyEvaluator is closed")
-        g = torch.as_tensor(grids, device=self.device)
-        if g.dtype != torch.uint8:
-            g = g.to(torch.uint8)
-        if g.dim() == 3:
-            g = g.unsqueeze(0)
-        if g.dim() != 4 or tuple(g.shape[1:]) != self.map_shape:
-            raise ValueError(f"grids must have shape [n]{list(self.map_shape)}, got {list(g.shape)}")
-        return g.contiguous()
 
     def _holes_arg(self, holes, n):
         h = torch.as_tensor(holes, device=self.device)
@@ -172,10 +148,8 @@ class Mc3dHoleyEvaluator:
         ERR_HOLE, ERR_QUEUE), play int32 [n][12] (MC3D_HOLEY_PLAY_KEYS), route_len and route2_len int32 [n], leg_len int32
         [n][2]; with route_cap > 0 coords and coords2 int16 [n][route_cap][3] ((x, y, z), -1 past the end); with overlay
         overlay and overlay2 bool [n][Z+2][Y+2][X+2].  The header says which route is which."""
-        g = self._grids_arg(grids)
+        g = self._levels_arg(grids)
         n = g.shape[0]
-        if n < 1:
-            raise ValueError("no levels to evaluate")
         h = self._holes_arg(holes, n)
         route_cap = int(route_cap)
         if route_cap < 0:
@@ -241,12 +215,3 @@ class Mc3dHoleyEvaluator:
             if k != "NONE":
                 out[:, j] = stats[:, self.stat_keys.index(k)]
         return out
-
-    def close(self):
-        self._workspace = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()

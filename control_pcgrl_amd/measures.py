@@ -1,7 +1,8 @@
 """The Python side of the measure / pack step and the pairwise Hamming step, written once: the entropy table, the result
 namespaces and their views (include/pcgrl_amd_measures.h, pcgrl_amd_smb_measures.h, pcgrl_amd_loderunner_measures.h; DESIGN.md
-sections 16, 24, 27, 29).  VecPcgrlEnv, SmbMeasures and LodeRunnerEvaluator mix it in; each keeps its choice of C entry point,
-its T and its checks of the grids argument.  file:line references are relative to the reference's control_pcgrl/ directory.
+sections 16, 24, 27, 29).  VecPcgrlEnv, SmbMeasures (for SmbVecEnv) and evaluator.py's LevelEvaluator, the base of the level
+evaluators, mix it in; each keeps its choice of C entry point, its T and its checks of the grids
+argument.  file:line references are relative to the reference's control_pcgrl/ directory.
 """
 from contextlib import nullcontext
 from types import SimpleNamespace

@@ -114,3 +114,21 @@ def target_interval(trg: Target):
                              "arange, control_wrappers.py:339) -- the map is too small for this problem's static targets")
         return float(lo), float(lo + n - 1)
     return float(trg), float(trg)
+
+
+def fill_targets(cfg, spec: ProblemSpec, weights, label="statistics"):
+    """What the level evaluators' <name>_config functions share: `weights` (None: the spec's defaults) must name statistics of
+    the spec, and per statistic the C config gets its weight and, where the spec has a static target for it, the zero-loss
+    interval and -- in a config struct that has the field -- has_trg.  A statistic without a target keeps the struct's zeros,
+    so it adds nothing to the loss whatever its weight.  `label` names the statistics in the refusal."""
+    weights = dict(spec.default_weights) if weights is None else dict(weights)
+    unknown = set(weights) - set(spec.stat_keys)
+    if unknown:
+        raise ValueError(f"unknown {label} in weights: {sorted(unknown)}")
+    for i, k in enumerate(spec.stat_keys):
+        cfg.weight[i] = float(weights.get(k, 0.0))
+        if k in spec.static_trgs:
+            if hasattr(cfg, "has_trg"):
+                cfg.has_trg[i] = 1
+            cfg.trg_lo[i], cfg.trg_hi[i] = target_interval(spec.static_trgs[k])
+    return cfg

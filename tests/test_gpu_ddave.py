@@ -14,6 +14,7 @@ import torch
 
 import ddave_levels as DL
 import ddave_rules as R
+from fixture_cases import fixture_cases
 import measures_numpy as mn
 from control_pcgrl_amd import _lib
 from control_pcgrl_amd.ddave import DDAVE_MEASURE_NAMES, DDaveEvaluator, ddave_config
@@ -22,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ddave")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "dd_*.npz")))
+CASES, CASE_IDS = fixture_cases(FILES)  # each file as ever, and split into several launches
 MEAS_FILES = sorted(glob.glob(os.path.join(GOLDEN, "meas_*.npz")))
 DEV = "cuda:0"
 T = 7
@@ -83,8 +85,8 @@ def assert_same(got, want, what=""):
         assert bad.size == 0, (what, k, "levels", bad[:8].tolist(), g[bad[0]].tolist(), want[k][bad[0]].tolist())
 
 
-@pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
-def test_kernel_equals_fixtures(path):
+@pytest.mark.parametrize("path,max_levels", CASES, ids=CASE_IDS)
+def test_kernel_equals_fixtures(path, max_levels):
     z = np.load(path)
     grids, power = z["grids"], int(z["power"])
     n, cap = len(grids), z["moves"].shape[1]
@@ -95,7 +97,7 @@ def test_kernel_equals_fixtures(path):
     ran = z["stage_won"] >= 0
     assert np.array_equal(np.where(ran, z["stage_iters"], 0), z["play"][:, 1:5])
     assert np.array_equal((z["stage_won"] == 1).any(1), want["won"])
-    with DDaveEvaluator(grids.shape[1:], DEV, solver_power=power, max_levels=256) as ev:
+    with DDaveEvaluator(grids.shape[1:], DEV, solver_power=power, max_levels=max_levels or 256) as ev:
         assert_same(ev.evaluate(grids, move_cap=cap), want, os.path.basename(path))
         ev.check_errors()
         # the reward and the episode end of the recorded pairs, bit for bit

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from fixture_cases import fixture_cases
 import loderunner_levels as LL
 import loderunner_rules as R
 from control_pcgrl_amd.loderunner import LodeRunnerEvaluator
@@ -18,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loderunner")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "*.npz")))
+CASES, CASE_IDS = fixture_cases(FILES)  # each file as ever, and split into several launches
 DEV = "cuda:0"
 # levels per shape: fewer at 16 x 32, where the plain-Python rules take tens of milliseconds per level
 GENERATED = [(8, 12, 2000), (4, 4, 2000), (1, 5, 2000), (5, 7, 2000), (16, 32, 60)]
@@ -70,15 +72,15 @@ def assert_same(got, want, what=""):
         assert bad.size == 0, (what, k, "levels", bad[:8].tolist(), g[bad[0]].tolist(), want[k][bad[0]].tolist())
 
 
-@pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
-def test_kernel_equals_fixtures(path):
+@pytest.mark.parametrize("path,max_levels", CASES, ids=CASE_IDS)
+def test_kernel_equals_fixtures(path, max_levels):
     z = np.load(path)
     grids = z["grids"]
     n, cap = len(grids), z["gold_state"].shape[1]
     want = {"stats": z["stats"], "loss": np.array([R.loss(s) for s in z["stats"]]), "error": np.zeros(n, np.int32),
             "play": np.column_stack([z["stats"][:, 0] == 1, z["landing"], z["collected"]]).astype(np.int32),
             "gold_state": z["gold_state"], "gold_dist": z["gold_dist"], "win": z["stats"][:, 3], "path_length": z["stats"][:, 4]}
-    with LodeRunnerEvaluator(grids.shape[1:], DEV) as ev:
+    with LodeRunnerEvaluator(grids.shape[1:], DEV, **({"max_levels": max_levels} if max_levels else {})) as ev:
         assert_same(ev.evaluate(grids, gold_cap=cap), want, os.path.basename(path))
         ev.check_errors()
 

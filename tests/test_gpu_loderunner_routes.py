@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from fixture_cases import fixture_cases
 import loderunner_levels as LL
 import loderunner_routes_expect as X
 import loderunner_rules as R
@@ -21,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loderunner_routes")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "*.npz")))
+CASES, CASE_IDS = fixture_cases(FILES)  # each file as ever, and split into several launches
 DEV = "cuda:0"
 ROUTE_KEYS = ("coords", "moves", "tour_len", "gold_off", "gold_back")
 EVAL_KEYS = ("stats", "loss", "play", "gold_state", "gold_dist", "error")
@@ -65,13 +67,13 @@ def assert_same_as_evaluate(got, ev_out):
         assert torch.equal(a, b), k
 
 
-@pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
-def test_kernel_equals_the_recorded_lists(path):
+@pytest.mark.parametrize("path,max_levels", CASES, ids=CASE_IDS)
+def test_kernel_equals_the_recorded_lists(path, max_levels):
     z = np.load(path)
     grids = z["grids"]
     pairs = [X.pairs_of_fixture(z, i) for i in range(len(grids))]
     cap = max(cap_for(pairs), int((grids == R.GOLD).reshape(len(grids), -1).sum(1).max()), 1)
-    with LodeRunnerEvaluator(grids.shape[1:], DEV) as ev:
+    with LodeRunnerEvaluator(grids.shape[1:], DEV, **({"max_levels": max_levels} if max_levels else {})) as ev:
         got = ev.routes(grids, gold_cap=cap, moves=True)
         assert_routes(got, pairs, cap, 8 * grids.shape[1] * grids.shape[2], os.path.basename(path))
         assert_same_as_evaluate(got, ev.evaluate(grids, gold_cap=cap))

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import measures_numpy as mn
+from fixture_cases import fixture_cases
 import microstructure_levels as ML
 import microstructure_rules as R
 from control_pcgrl_amd import _lib
@@ -22,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "microstructure")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "*.npz")))
+CASES, CASE_IDS = fixture_cases(FILES)  # each file as ever, and split into several launches
 DEV = "cuda:0"
 T = 2
 # maps per shape: fewer where the plain-Python rules are slow
@@ -76,8 +78,8 @@ def _np(t):
     return t.cpu().numpy()
 
 
-@pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
-def test_kernel_equals_fixtures(path):
+@pytest.mark.parametrize("path,max_levels", CASES, ids=CASE_IDS)
+def test_kernel_equals_fixtures(path, max_levels):
     z = np.load(path)
     grids = z["grids"]
     n, cap = len(grids), z["region_rec"].shape[1]
@@ -85,7 +87,7 @@ def test_kernel_equals_fixtures(path):
     want = {"stats": stats, "loss": np.array([R.loss(s) for s in stats]), "regions": z["regions"],
             "error": np.zeros(n, np.int32), "region_rec": z["region_rec"], "region_tort": z["region_tort_bits"].view(np.float64),
             "path_length": stats[:, 0], "tortuosity": stats[:, 1]}
-    with MicrostructureEvaluator(grids.shape[1:], DEV) as ev:
+    with MicrostructureEvaluator(grids.shape[1:], DEV, **({"max_levels": max_levels} if max_levels else {})) as ev:
         assert_same(ev.evaluate(grids, region_cap=cap), want, os.path.basename(path))
         ev.check_errors()
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from fixture_cases import fixture_cases
 import smb_levels as SL
 import smb_rules as R
 from control_pcgrl_amd.smb import SmbEvaluator
@@ -17,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "smb")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "*.npz")))
+CASES, CASE_IDS = fixture_cases(FILES)  # each file as ever, and split into several launches
 DEV = "cuda:0"
 SHAPES = [(16, 116), (16, 128), (16, 64), (16, 65), (4, 1), (5, 7), (16, 24)]  # 64 | 65: one | two columns per lane
 
@@ -58,8 +60,8 @@ def assert_same(got, want, what=""):
         assert bad.size == 0, (what, k, "levels", bad[:8].tolist(), g[bad[0]].tolist(), want[k][bad[0]].tolist())
 
 
-@pytest.mark.parametrize("path", FILES, ids=[os.path.basename(f)[:-4] for f in FILES])
-def test_kernel_equals_fixtures(path):
+@pytest.mark.parametrize("path,max_levels", CASES, ids=CASE_IDS)
+def test_kernel_equals_fixtures(path, max_levels):
     z = np.load(path)
     grids, power = z["grids"], int(z["solver_power"])
     n = len(grids)
@@ -83,11 +85,11 @@ def test_kernel_equals_fixtures(path):
     assert (fin[:, 3] == z["stats"][:, 5]).all()
     want = {"stats": z["stats"], "loss": z["loss"], "won": won != 0, "play": play, "moves": want_moves,
             "length": np.asarray(pick("length"), np.int32), "jump_locs": want_locs}
-    with SmbEvaluator(grids.shape[1:], DEV, solver_power=power, max_levels=n) as ev:
+    with SmbEvaluator(grids.shape[1:], DEV, solver_power=power, max_levels=max_levels or n) as ev:
         assert_same(ev.evaluate(grids, cap=cap, jump_cap=jump_cap), want, "default weights")
         ev.check_errors()
     alt = dict(zip(R.STAT_KEYS, z["alt_weights"].tolist()))
-    with SmbEvaluator(grids.shape[1:], DEV, solver_power=power, weights=alt, max_levels=n) as ev:
+    with SmbEvaluator(grids.shape[1:], DEV, solver_power=power, weights=alt, max_levels=max_levels or n) as ev:
         got = ev.evaluate(grids, playthrough=False)
         assert set(got) == {"stats", "loss", "won", "play"}
         assert np.array_equal(got["loss"].cpu().numpy(), z["loss_alt"]) and np.array_equal(got["stats"].cpu().numpy(), z["stats"])

@@ -124,6 +124,8 @@ def test_fixtures_through_evaluator_measures(path):
         ev.measures(torch.zeros((2, H, W + 1), dtype=torch.uint8))
     ev.check_errors()
     ev.close()
+    with pytest.raises(RuntimeError, match="closed"):
+        ev.measures(torch.as_tensor(grids))
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=fixture_id)

@@ -157,11 +157,8 @@ def test_header_units_symbols_and_config():
     text = re.sub(r"/\*.*?\*/", "", open(_lib.MICROSTRUCTURE_HEADER).read(), flags=re.S)
     declared = set(re.findall(r"\b(pcgrl_[a-z0-9_]+)\s*\(", text))
     assert declared == SYMBOLS == set(_lib.MICROSTRUCTURE_SYMBOLS)
-    others = [_lib.SYMBOLS, _lib.CODES_SYMBOLS, _lib.ASYNC3D_SYMBOLS, _lib.PATHS_SYMBOLS, _lib.SOLUTIONS_SYMBOLS,
-              _lib.MULTIAGENT_SYMBOLS, _lib.MEASURES_SYMBOLS, _lib.SMB_SYMBOLS, _lib.SMB_ENV_SYMBOLS, _lib.SMB_READY_SYMBOLS,
-              _lib.SMB_STATE_SYMBOLS, _lib.SMB_ROLLOUT_SYMBOLS, _lib.SMB_CTRL_SYMBOLS, _lib.SMB_VECTOR_SYMBOLS,
-              _lib.SMB_MEASURES_SYMBOLS, _lib.LODERUNNER_SYMBOLS, _lib.LODERUNNER_MEASURES_SYMBOLS,
-              _lib.LODERUNNER_ROUTES_SYMBOLS]
+    others = [table for _, table in _lib.ABI if table is not _lib.MICROSTRUCTURE_SYMBOLS]
+    assert len(others) == len(_lib.ABI) - 1
     assert not any(declared & set(o) for o in others)
     L = _lib.lib()
     for name in declared:

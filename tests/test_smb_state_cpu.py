@@ -39,8 +39,8 @@ def test_lib_lists_the_unit_the_header_and_the_symbols():
     assert set(_lib.SMB_STATE_SYMBOLS) == declared and len(declared) == 6
     code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     assert set(re.findall(r"\b(pcgrl_\w+)\(", code)) == declared  # nothing else is declared here
-    others = (_lib.SYMBOLS, _lib.CODES_SYMBOLS, _lib.ASYNC3D_SYMBOLS, _lib.PATHS_SYMBOLS, _lib.SOLUTIONS_SYMBOLS,
-              _lib.MULTIAGENT_SYMBOLS, _lib.MEASURES_SYMBOLS, _lib.SMB_SYMBOLS, _lib.SMB_ENV_SYMBOLS, _lib.SMB_READY_SYMBOLS)
+    others = [table for _, table in _lib.ABI if table is not _lib.SMB_STATE_SYMBOLS]
+    assert len(others) == len(_lib.ABI) - 1
     for table in others:
         assert not declared & set(table)
     for path in (_lib.HEADER, _lib.SMB_HEADER, _lib.SMB_ENV_HEADER, _lib.SMB_READY_HEADER):  # and no other header declares them
