@@ -39,6 +39,10 @@ Drop-in for the reference's env hot path only (control_pcgrl/rl/envs.py:make_env
   NcaGenerator             the NCA level generator (the reference's default `--model NCA --representation cellular`): G
                            genomes x S seeds rolled out to their final maps in one launch, bit for bit the numpy twins of
                            control_pcgrl_amd.nca; generator_for(evaluator_or_env) builds the one for an evaluator's maps
+  Nca3dGenerator           the 3-D NCA level generator (`--model NCA3D`, cellular3D and cellular3Dholey): the same for maps of
+                           3..16 cells an axis, plain or reading the bordered map with its holes, bit for bit the numpy twins
+                           of control_pcgrl_amd.nca3d; generator3d_for(evaluator) builds the holey one for a
+                           Mc3dHoleyEvaluator, and mc3d_holey_score() is its score in NcaEvolution
   GenomeArchive            the same archive with a genome (float32 [P]) as the elite: ask() hands out Gaussian children with
                            stated arithmetic, sample() the first generation; aggregate() is simulate's fold over a genome's
                            seeds; NcaEvolution chains ask -> generate -> score -> aggregate -> add with no host sync
@@ -66,12 +70,14 @@ from .mc3d_holey import Mc3dHoleyEvaluator, all_holes, fixed_holes, mc3d_holey_s
 from .archive import DeviceGridArchive, archive_for  # noqa: F401
 from . import nca  # noqa: F401
 from .nca import NcaGenerator, generator_for  # noqa: F401
+from . import nca3d  # noqa: F401
+from .nca3d import Nca3dGenerator, generator3d_for  # noqa: F401
 
 __version__ = "0.7.0"  # csrc/pcgrl_engine.hip pcgrl_version() carries the same number
 
 # The evolution layer (evo.py) is imported at first use, so that importing the package for the env engine alone does what it
 # did before that layer existed: `from control_pcgrl_amd import GenomeArchive` and `control_pcgrl_amd.evo` work as usual.
-_EVO_EXPORTS = ("GenomeArchive", "NcaEvolution", "aggregate", "evaluator_score", "genome_archive_for")
+_EVO_EXPORTS = ("GenomeArchive", "NcaEvolution", "aggregate", "evaluator_score", "genome_archive_for", "mc3d_holey_score")
 
 
 def __getattr__(name):

@@ -52,6 +52,7 @@ MDUNGEON_HEADER = _include("pcgrl_amd_mdungeon.h")
 ARCHIVE_HEADER = _include("pcgrl_amd_archive.h")
 MC3D_HOLEY_HEADER = _include("pcgrl_amd_mc3d_holey.h")
 NCA_HEADER = _include("pcgrl_amd_nca.h")
+NCA3D_HEADER = _include("pcgrl_amd_nca3d.h")
 EVO_HEADER = _include("pcgrl_amd_evo.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-falign-loops=32", "-fPIC"]
 
@@ -430,6 +431,16 @@ NCA_SYMBOLS = {
     "pcgrl_nca_last_error": (C.c_char_p, []),
 }
 
+# include/pcgrl_amd_nca3d.h: the 3-D NCA level generator, plain and holey (a handle of its own)
+NCA3D_SYMBOLS = {
+    "pcgrl_nca3d_create": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_void_p)]),
+    "pcgrl_nca3d_destroy": (None, [C.c_void_p]),
+    "pcgrl_nca3d_generate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+                             + [C.c_int32] * 4 + [C.c_void_p] * 4),
+    "pcgrl_nca3d_poll_error": (C.c_int, [C.c_void_p] * 2),
+    "pcgrl_nca3d_last_error": (C.c_char_p, []),
+}
+
 # include/pcgrl_amd_evo.h: NCA evolution (genome archives on the archive's handle, Gaussian children, simulate's fold over seeds;
 # the kernels are csrc/evo/pcgrl_evo.h, compiled into the archive's unit so that the insertion is written once)
 PCGRL_EVO_MAX_PARAMS = 16384
@@ -470,6 +481,7 @@ ABI = [("pcgrl_amd.h", SYMBOLS),
        ("pcgrl_amd_archive.h", ARCHIVE_SYMBOLS),
        ("pcgrl_amd_mc3d_holey.h", MC3D_HOLEY_SYMBOLS),
        ("pcgrl_amd_nca.h", NCA_SYMBOLS),
+       ("pcgrl_amd_nca3d.h", NCA3D_SYMBOLS),
        ("pcgrl_amd_evo.h", EVO_SYMBOLS)]
 ABI_HEADERS = [_include(name) for name, _ in ABI]
 

@@ -81,6 +81,69 @@ __device__ __forceinline__ float nca_s32(float xf) {
   return (float)((x >= 0.0 ? 1.0 : t) / (1.0 + t));
 }
 
+// layers 2 and 3 of CPL cells whose h1 is in registers: logits into acc3 (the stated order: ascending input channel from the
+// bias).  w2 [32][32] as in the genome, w3t [32][TP] (w3[i][c] at c * TP + i, zero-padded), all in LDS; the 3-D generator
+// (nca3d/pcgrl_nca3d.h) calls this too.
+template <int T, int CPL>
+__device__ __forceinline__ void nca_layers23(const float (&h1)[CPL][NCA_HID], const float *w2, const float *b2,
+                                             const float *w3t, const float *b3, float (&acc3)[CPL][T]) {
+  constexpr int TP = nca_tp(T);
+#pragma unroll
+  for (int k = 0; k < CPL; k++) {
+#pragma unroll
+    for (int i = 0; i < T; i++) acc3[k][i] = b3[i];
+  }
+#pragma unroll 1
+  for (int o = 0; o < NCA_HID; o++) {
+    float wr[NCA_HID], w3r[TP];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const float4 v = ((const float4 *)(w2 + o * 32))[q];
+      wr[q * 4 + 0] = v.x, wr[q * 4 + 1] = v.y, wr[q * 4 + 2] = v.z, wr[q * 4 + 3] = v.w;
+    }
+#pragma unroll
+    for (int q = 0; q < TP / 4; q++) {
+      const float4 v = ((const float4 *)(w3t + o * TP))[q];
+      w3r[q * 4 + 0] = v.x, w3r[q * 4 + 1] = v.y, w3r[q * 4 + 2] = v.z, w3r[q * 4 + 3] = v.w;
+    }
+    const float bias = b2[o];
+#pragma unroll
+    for (int k = 0; k < CPL; k++) {
+      float acc = bias;
+#pragma unroll
+      for (int c = 0; c < NCA_HID; c++) acc = acc + wr[c] * h1[k][c];
+      const float h2 = nca_relu(acc);
+#pragma unroll
+      for (int i = 0; i < T; i++) acc3[k][i] = acc3[k][i] + w3r[i] * h2;
+    }
+  }
+}
+
+// the pick: the first index at which s32(logit) is largest (the shortcut is in the head of this file); `finite` says whether
+// every logit is finite
+template <int T>
+__device__ __forceinline__ int nca_pick(const float (&logit)[T], bool &finite) {
+  float lmax = logit[0];
+  int j = 0;
+  finite = fabsf(logit[0]) <= FLT_MAX;
+#pragma unroll
+  for (int i = 1; i < T; i++) {
+    finite = finite && fabsf(logit[i]) <= FLT_MAX;
+    if (logit[i] > lmax) lmax = logit[i], j = i;
+  }
+  int win = j;
+  if (j > 0 && finite) {
+    const float smax = nca_s32(lmax);
+#pragma unroll
+    for (int i = T - 2; i >= 0; i--) {
+      const float l = logit[i];
+      const bool cannot_tie = lmax - l > 1.0f && l < 12.0f && lmax > -87.0f;
+      if (i < j && !cannot_tie && nca_s32(l) == smax) win = i;
+    }
+  }
+  return win;
+}
+
 template <int T, int CPL>
 __global__ void __launch_bounds__(NCA_MAX_THREADS) nca_kernel(NcaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char nca_smem[];
@@ -194,56 +257,12 @@ __global__ void __launch_bounds__(NCA_MAX_THREADS) nca_kernel(NcaArgs a) {
           }
         }
         float acc3[CPL][T];
-#pragma unroll
-        for (int k = 0; k < CPL; k++) {
-#pragma unroll
-          for (int i = 0; i < T; i++) acc3[k][i] = b3[i];
-        }
-#pragma unroll 1
-        for (int o = 0; o < NCA_HID; o++) {
-          float wr[NCA_HID], w3r[TP];
-#pragma unroll
-          for (int q = 0; q < 8; q++) {
-            const float4 v = ((const float4 *)(w2 + o * 32))[q];
-            wr[q * 4 + 0] = v.x, wr[q * 4 + 1] = v.y, wr[q * 4 + 2] = v.z, wr[q * 4 + 3] = v.w;
-          }
-#pragma unroll
-          for (int q = 0; q < TP / 4; q++) {
-            const float4 v = ((const float4 *)(w3t + o * TP))[q];
-            w3r[q * 4 + 0] = v.x, w3r[q * 4 + 1] = v.y, w3r[q * 4 + 2] = v.z, w3r[q * 4 + 3] = v.w;
-          }
-          const float bias = b2[o];
-#pragma unroll
-          for (int k = 0; k < CPL; k++) {
-            float acc = bias;
-#pragma unroll
-            for (int c = 0; c < NCA_HID; c++) acc = acc + wr[c] * h1[k][c];
-            const float h2 = nca_relu(acc);
-#pragma unroll
-            for (int i = 0; i < T; i++) acc3[k][i] = acc3[k][i] + w3r[i] * h2;
-          }
-        }
+        nca_layers23<T, CPL>(h1, w2, b2, w3t, b3, acc3);
 #pragma unroll
         for (int k = 0; k < CPL; k++) {
           const int cell = base + k * nthr + tid;
-          float lmax = acc3[k][0];
-          int j = 0;
-          bool finite = fabsf(acc3[k][0]) <= FLT_MAX;
-#pragma unroll
-          for (int i = 1; i < T; i++) {
-            finite = finite && fabsf(acc3[k][i]) <= FLT_MAX;
-            if (acc3[k][i] > lmax) lmax = acc3[k][i], j = i;
-          }
-          int win = j;
-          if (j > 0 && finite) {
-            const float smax = nca_s32(lmax);
-#pragma unroll
-            for (int i = T - 2; i >= 0; i--) {
-              const float l = acc3[k][i];
-              const bool cannot_tie = lmax - l > 1.0f && l < 12.0f && lmax > -87.0f;
-              if (i < j && !cannot_tie && nca_s32(l) == smax) win = i;
-            }
-          }
+          bool finite;
+          const int win = nca_pick<T>(acc3[k], finite);
           if (cell < cells) {
             nxt[cell] = (uint8_t)win;
             mine |= (win != cur[cell] ? 1u : 0u) | (finite ? 0u : 2u);

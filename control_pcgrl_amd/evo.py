@@ -279,16 +279,18 @@ class GenomeArchive(DeviceGridArchive):
         return state
 
 
-def genome_archive_for(evaluator_or_env, names, bins=100, device=None):
+def genome_archive_for(evaluator_or_env, names, bins=100, device=None, n_params=None):
     """The genome archive for the behaviour characteristics `names` of an evaluator or a 2-D VecPcgrlEnv: the dims and bounds
-    of archive_for, and genomes of nca.n_params(spec.n_tiles) weights."""
+    of archive_for, and genomes of nca.n_params(spec.n_tiles) weights -- or of `n_params` weights, as a generator's n_params
+    gives them (the 3-D generator's genomes are nca3d.n_params(spec.n_tiles) long)."""
     e = evaluator_or_env
     spec = getattr(e, "spec", None)
     if spec is None or not hasattr(spec, "n_tiles") or not hasattr(spec, "cond_bounds"):
         raise TypeError(f"genome_archive_for takes an evaluator or a VecPcgrlEnv, not {type(e).__name__}: it needs the problem's "
                         "cond_bounds and tiles")
     dims, bounds = archive_shape(spec, names, bins)
-    return GenomeArchive(dims, bounds, nca.n_params(spec.n_tiles), device=e.device if device is None else device)
+    return GenomeArchive(dims, bounds, nca.n_params(spec.n_tiles) if n_params is None else int(n_params),
+                         device=e.device if device is None else device)
 
 
 _AGG_FIELDS = (("behaviours", torch.float64), ("objective", torch.float64), ("time_penalty", torch.int32),
@@ -343,10 +345,40 @@ def evaluator_score(evaluator, names, **evaluate_kwargs):
     return score
 
 
+def mc3d_holey_score(evaluator, names, holes):
+    """The ready-made `score` of NcaEvolution for a Mc3dHoleyEvaluator, whose evaluate() and behaviour() take the holes of every
+    level: levels [n S, Z, Y, X] -> (-evaluate(levels, holes)["loss"], the statistics `names` as behaviour).  holes is int32
+    [2, 3] (all levels) or [S, 2, 3] (per seed: repeated for the n genomes, seeds fastest, as the levels are laid out) --
+    the same holes generation(..., holes=) gives the generator."""
+    names = [names] if isinstance(names, str) else list(names)
+    evaluator.check_names(names)
+    h = torch.as_tensor(holes, device=evaluator.device).to(torch.int32)
+    if tuple(h.shape) != (2, 3) and (h.dim() != 3 or tuple(h.shape[1:]) != (2, 3)):
+        raise ValueError(f"holes must be [2, 3] or [S, 2, 3], got {list(h.shape)}")
+
+    def score(levels):
+        hl = h
+        if h.dim() == 3:
+            S = h.shape[0]
+            if levels.shape[0] % S:
+                raise ValueError(f"{levels.shape[0]} levels are not a whole number of genomes of {S} seeds")
+            hl = h.repeat(levels.shape[0] // S, 1, 1)  # [n S, 2, 3]
+        res = evaluator.evaluate(levels, hl)
+        beh = torch.zeros((levels.shape[0], len(names)), dtype=torch.float64, device=evaluator.device)
+        for j, k in enumerate(names):
+            if k != "NONE":
+                beh[:, j] = res["stats"][:, evaluator.stat_keys.index(k)]
+        return -res["loss"], beh
+
+    score.evaluator = evaluator
+    return score
+
+
 class NcaEvolution:
     """One generation of the reference's NCA evolution on the device: generation() runs archive.ask (or sample) ->
     generator.generate -> score(levels [n S, H, W]) -> (objective [n S], behaviours [n S, D]) -> aggregate -> diversity(group=S)
-    where the score's evaluator has it -> archive.add, all enqueued on the current stream with no host sync.  The buffers of the
+    where the score's evaluator has it (no 3-D evaluator has: there is no 3-D diversity kernel, so the bonus of a 3-D
+    generation is None) -> archive.add, all enqueued on the current stream with no host sync.  The buffers of the
     library calls are allocated at the first call of a given (n, S) and reused, so a later generation allocates nothing in
     the library and the whole call can be captured in a HIP graph (the evaluators' own outputs come from torch's allocator)."""
 
@@ -359,12 +391,12 @@ class NcaEvolution:
     def _buffers(self, n, S):
         key = (n, S)
         if key not in self._buf:
-            a, H, W = self.archive, *self.generator.map_shape
+            a, dims = self.archive, tuple(self.generator.map_shape)
             dev, D = a.device, len(a.dims)
             self._buf[key] = SimpleNamespace(
                 genomes=torch.empty((n, a.n_params), dtype=torch.float32, device=dev),
                 parent=torch.empty(n, dtype=torch.int32, device=dev),
-                gen=SimpleNamespace(levels=torch.empty((n, S, H, W), dtype=torch.uint8, device=dev),
+                gen=SimpleNamespace(levels=torch.empty((n, S) + dims, dtype=torch.uint8, device=dev),
                                     n_step=torch.empty((n, S), dtype=torch.int32, device=dev), frames=None),
                 agg=SimpleNamespace(behaviours=torch.empty((n, D), dtype=torch.float64, device=dev),
                                     objective=torch.empty(n, dtype=torch.float64, device=dev),
@@ -373,22 +405,24 @@ class NcaEvolution:
                                     valid=torch.empty(n, dtype=torch.uint8, device=dev)))
         return self._buf[key]
 
-    def generation(self, init_states, n, seed, sigma=0.1, first=False, mean=None):
+    def generation(self, init_states, n, seed, sigma=0.1, first=False, mean=None, holes=None):
         """n children (first=True: samples around `mean`), each rolled out on the S init_states uint8 [S, H, W] (or
-        [n, S, H, W]), scored, folded over its seeds and inserted.  Returns a namespace: added (the add result), aggregate,
+        [n, S, H, W]; with a 3-D generator [S, Z, Y, X] or [n, S, Z, Y, X]), scored, folded over its seeds and inserted.
+        `holes` (a holey 3-D generator's: [2, 3] or [S, 2, 3]) is passed through to generate().
+        Returns a namespace: added (the add result), aggregate,
         diversity_bonus (float64 [n], or None -- reported, not added to the objective, as in the reference), genomes,
         parent_cell (None for a first generation), levels and n_step.  The tensors are reused by the next call."""
         n = int(n)
         init = torch.as_tensor(init_states, device=self.archive.device)
-        S = init.shape[-3]
+        dims = tuple(self.generator.map_shape)
+        S = init.shape[-len(dims) - 1]
         b = self._buffers(n, S)
         if first:
             self.archive.sample(n, seed=seed, sigma=sigma, mean=mean, out=b.genomes)
         else:
             self.archive.ask(n, seed=seed, sigma=sigma, out=(b.genomes, b.parent))
-        gen = self.generator.generate(b.genomes, init, out=b.gen)
-        H, W = self.generator.map_shape
-        levels = gen.levels.view(n * S, H, W)
+        gen = self.generator.generate(b.genomes, init, out=b.gen, **({} if holes is None else {"holes": holes}))
+        levels = gen.levels.view((n * S,) + dims)
         objective, behaviours = self.score(levels)
         agg = aggregate(objective.reshape(n, S), behaviours.reshape(n, S, -1), gen.n_step, weight=self.weight, out=b.agg)
         bonus = None
